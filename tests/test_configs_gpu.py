@@ -485,7 +485,7 @@ def test_bench_two_ranks_spawned_by_bench_itself():
     two = torch.cuda.device_count() >= 2
     extra_env = {} if two else {'RCF_BENCH_SINGLE_DEVICE': '1', 'RCF_DIST_BACKEND': 'gloo'}
     args = ['--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '2', '--height', '224', '--width', '384', '--points', '32',
-            '--preheat-s', '0', '--no-cpu-baseline']
+            '--preheat-s', '0', '--no-cpu-baseline', '--full']
     try:
         r, rec = _run_bench(args, extra_env, timeout=240)     # normally 10-20 s
     except subprocess.TimeoutExpired:
@@ -511,7 +511,7 @@ def test_bench_eight_ranks_spawned_by_bench_itself():
     eight = torch.cuda.device_count() >= 8
     extra_env = {} if eight else {'RCF_BENCH_SINGLE_DEVICE': '1', 'RCF_DIST_BACKEND': 'gloo'}
     args = ['--gpus', '8', '--steps', '2', '--warmup', '1', '--batch', '2', '--height', '224', '--width', '384', '--points', '32',
-            '--preheat-s', '0', '--no-cpu-baseline']
+            '--preheat-s', '0', '--no-cpu-baseline', '--full']
     try:
         r, rec = _run_bench(args, extra_env, timeout=600)
     except subprocess.TimeoutExpired:
@@ -539,7 +539,7 @@ def test_bench_two_ranks_at_the_headline_shape_pass_their_own_loss_check(dtype):
     value within bf16's forward error (measured 3e-6 .. 1e-4 on one rank; bar 5e-3).'''
     two = torch.cuda.device_count() >= 2
     extra_env = {} if two else {'RCF_BENCH_SINGLE_DEVICE': '1', 'RCF_DIST_BACKEND': 'gloo'}
-    args = ['--gpus', '2', '--steps', '2', '--warmup', '1', '--preheat-s', '0', '--no-cpu-baseline', '--dtype', dtype]
+    args = ['--gpus', '2', '--steps', '2', '--warmup', '1', '--preheat-s', '0', '--no-cpu-baseline', '--dtype', dtype, '--full']
     r, rec = _run_bench(args, extra_env, timeout=900)
     assert r.returncode == 0 and rec is not None, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
     assert rec['n_gpus'] == 2 and rec['rccl_ranks'] == 2 and rec['config']['global_batch'] == 16 and rec['dtype'] == dtype
@@ -559,7 +559,7 @@ def test_bench_single_gpu_line_carries_the_contract_fields():
     '''The driver's command (`python bench.py`, defaults) with few steps: the contract fields, the headline's own loss check, and the
     legs that ride in the same line -- `exact_tier` (the step on three bf16 planes) and `other_configs` (BASELINE.json configs[2..4]),
     each checked against the CPU oracle's recorded values by bench.py itself.  No clock enters an assertion.'''
-    r, rec = _run_bench(['--steps', '2', '--warmup', '1', '--preheat-s', '0', '--no-cpu-baseline', '--leg-steps', '2'], timeout=900)
+    r, rec = _run_bench(['--steps', '2', '--warmup', '1', '--preheat-s', '0', '--no-cpu-baseline', '--leg-steps', '2', '--full'], timeout=900)
     assert r.returncode == 0 and rec is not None, (r.returncode, r.stderr[-1500:])
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
                 'dtype', 'data', 'config', 'roofline', 'algorithmic_tflops'):
@@ -586,10 +586,41 @@ def test_bench_single_gpu_line_carries_the_contract_fields():
     print({k: (v['value'], v['unit'], v['check']) for k, v in others.items()})
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_on_every_run(tmp_path):
+    '''A run without --full prints the headline alone (no legs, no roofline, no oracle checks) and times exactly --steps steps;
+    --dump-outputs writes the last timed step's loss, output and a parameter sample, and two runs with the same arguments write the
+    same arrays, however many steps their time-bounded pre-heats ran (those steps are rolled back).'''
+    args = ['--steps', '3', '--warmup', '1', '--batch', '2', '--height', '224', '--width', '384', '--points', '32', '--preheat-s', '1']
+    recs = []
+    for run in ('a', 'b'):
+        r, rec = _run_bench(args + ['--dump-outputs', str(tmp_path / run)], timeout=600)
+        assert r.returncode == 0 and rec is not None, (r.returncode, r.stderr[-1500:])
+        recs.append(rec)
+    rec = recs[0]
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in rec, key
+    assert rec['steps'] == 3 and rec['dtype'] == 'f32' and rec['value'] > 0 and rec['ms_per_step'] > 0
+    for key in ('roofline', 'cpu_baseline', 'exact_tier', 'other_configs', 'dp'):
+        assert key not in rec, key
+    assert 'loss_check' not in rec['config'] and 'arithmetic' not in rec['config']
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b'))
+    eager = rec['config']['launch_probe']['decision'] == 'eager'
+    assert names == sorted(['loss.npy', 'parameters_sample.npy'] + (['output_depth.npy'] if eager else [])), names
+    loss = np.load(tmp_path / 'a' / 'loss.npy')
+    assert loss.dtype == np.float64 and abs(float(loss) - rec['config']['final_loss']) < 1e-4 * abs(float(loss))
+    assert np.load(tmp_path / 'a' / 'parameters_sample.npy').dtype == np.float32
+    if eager:
+        out = np.load(tmp_path / 'a' / 'output_depth.npy')
+        assert out.dtype == np.float32 and out.shape == (2, 1, 224, 384) and np.isfinite(out).all()
+    for name in names:
+        np.testing.assert_allclose(np.load(tmp_path / 'b' / name), np.load(tmp_path / 'a' / name), rtol=1e-5, atol=1e-7, err_msg=name)
+
+
 def test_bench_falls_back_to_the_replayed_graph_on_a_host_bound_box():
     '''A host that cannot enqueue a step as fast as the GPU runs it (forced here: threshold 0) gets the replayed graph in the headline
     AND in the training legs, the line says so, and every oracle check still passes.'''
-    r, rec = _run_bench(['--steps', '2', '--warmup', '1', '--preheat-s', '0', '--no-cpu-baseline', '--leg-steps', '2'],
+    r, rec = _run_bench(['--steps', '2', '--warmup', '1', '--preheat-s', '0', '--no-cpu-baseline', '--leg-steps', '2', '--full'],
                         env_extra={'RCF_BENCH_HOST_BOUND_FRAC': '0'}, timeout=900)
     assert r.returncode == 0 and rec is not None, (r.returncode, r.stderr[-1500:])
     probe = rec['config']['launch_probe']

@@ -370,6 +370,27 @@ def test_bench_refuses_to_measure_fewer_gpus_than_asked(pkg):
     assert r.returncode != 0 and '"metric"' not in r.stdout
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_the_same_sample_every_time(tmp_path):
+    '''bench.py --dump-outputs: float64 stays float64, everything else (bf16 included) is written as float32; an output larger than
+    DUMP_SAMPLE elements becomes <name>_sample.npy with the same seeded indices on every call; more than 64 MB in all is refused.'''
+    import bench
+    n = bench.DUMP_SAMPLE
+    big = torch.arange(n + 1000, dtype=torch.float32)
+    arrays = {'loss': torch.tensor(1.25, dtype=torch.float64), 'small': torch.arange(6, dtype=torch.bfloat16).reshape(2, 3), 'big': big}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(tmp_path / 'a')) == ['big_sample.npy', 'loss.npy', 'small.npy']
+    loss, small = np.load(tmp_path / 'a' / 'loss.npy'), np.load(tmp_path / 'a' / 'small.npy')
+    assert loss.dtype == np.float64 and float(loss) == 1.25
+    assert small.dtype == np.float32 and small.shape == (2, 3) and small.ravel().tolist() == list(range(6))
+    sample = np.load(tmp_path / 'a' / 'big_sample.npy')
+    assert sample.dtype == np.float32 and sample.shape == (n,)
+    assert np.all(np.diff(sample) > 0) and sample[0] >= 0 and sample[-1] < n + 1000     # distinct elements in index order
+    np.testing.assert_array_equal(sample, np.load(tmp_path / 'b' / 'big_sample.npy'))
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / 'c'), {'x%d' % i: big for i in range(5)})
+
+
 def test_bench_expected_loss_fixture_is_the_oracle_on_the_bench_inputs(pkg):
     '''tests/golden/bench_expected.json (what bench.py checks its first training step against) is reproduced here for its small case.'''
     import json

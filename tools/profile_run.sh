@@ -8,17 +8,17 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 # duration and counters are its own, as in bench.py's roofline events; the bench lines themselves run the default (side stream on)
 out=gpurun_out/prof_$tag
 mkdir -p $out/pmc
-python3 bench.py --steps 20 --warmup 5 > $out/bench_line.log 2> $out/bench_line.err
-python3 bench.py --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_bf16.log 2>&1
-python3 bench.py --dtype f32_3plane --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_f32_3plane.log 2>&1
-python3 bench.py --workload infer --steps 20 --warmup 5 > $out/bench_infer.log 2>&1
-python3 bench.py --workload radarnet --steps 10 --warmup 3 > $out/bench_radarnet.log 2>&1
-python3 bench.py --workload infer --dtype f32 --steps 10 --warmup 3 > $out/bench_infer_f32.log 2>&1
-python3 bench.py --workload radarnet --dtype f32 --steps 10 --warmup 3 > $out/bench_radarnet_f32.log 2>&1
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_line.log 2> $out/bench_line.err
+python3 bench.py --full --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_bf16.log 2>&1
+python3 bench.py --full --dtype f32_3plane --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_f32_3plane.log 2>&1
+python3 bench.py --full --workload infer --steps 20 --warmup 5 > $out/bench_infer.log 2>&1
+python3 bench.py --full --workload radarnet --steps 10 --warmup 3 > $out/bench_radarnet.log 2>&1
+python3 bench.py --full --workload infer --dtype f32 --steps 10 --warmup 3 > $out/bench_infer_f32.log 2>&1
+python3 bench.py --full --workload radarnet --dtype f32 --steps 10 --warmup 3 > $out/bench_radarnet_f32.log 2>&1
 # the traced / counted fp32 runs are the HEADLINE step alone (--no-side-leg --no-other-configs: the default line's extra legs would mix four
 # workloads into one kernel table)
 # eager launches under the profiler (a replayed hipGraph hides the per-launch events bench.py's roofline uses)
-RCF_SINGLE_STREAM=1 rocprofv3 --kernel-trace --stats -d /tmp/trace_$tag -o r -- python3 bench.py --graph 0 --steps 5 --warmup 3 --preheat-s 0 --no-cpu-baseline --no-side-leg --no-other-configs > $out/trace.log 2>&1
+RCF_SINGLE_STREAM=1 rocprofv3 --kernel-trace --stats -d /tmp/trace_$tag -o r -- python3 bench.py --full --graph 0 --steps 5 --warmup 3 --preheat-s 0 --no-cpu-baseline --no-side-leg --no-other-configs > $out/trace.log 2>&1
 grep "^{" $out/trace.log | tail -1 > $out/trace_bench_line.json
 python3 tools/trace_summary.py /tmp/trace_$tag 8 60 > $out/fp32_train_kernels.txt
 RCF_SINGLE_STREAM=1 rocprofv3 --kernel-trace --stats -d /tmp/trace_b16_$tag -o r -- python3 bench.py --dtype bf16 --graph 0 --steps 5 --warmup 3 --preheat-s 0 --no-cpu-baseline > $out/trace_b16.log 2>&1
