@@ -16,6 +16,7 @@ the tensor is never written; any other consumer materialises it once, on demand 
 '''
 
 import os
+from collections import namedtuple
 
 import torch
 
@@ -30,7 +31,7 @@ class WeightPlan(object):
     layers), each a 4-5 us launch of a few thousand elements: ~1 ms of GPU time and a fifth of the step's launches.  The weights
     do not change between the start of the forward pass and the end of the backward pass, so they can all be packed up front.
 
-    The plan is positional.  In the first training step (state 'record') the engine's _phase_w / _pack / _pack_n do their work one
+    The plan is positional.  In the first training step (state 'record') the engine's _phase_w / _pack_n do their work one
     launch at a time, as without a plan, into PERSISTENT buffers and note (kind, descriptor, source pointers, buffer).  end() seals
     the list into two ctypes arrays.  From then on (state 'replay') begin() issues rcf_phase_weights_batch +
     rcf_conv2d_pack_weights_batch over the arrays -- they read the parameters' current values -- and the i-th request of the step
@@ -169,6 +170,13 @@ class Act(object):
                                     # writer of g clears them (stale)
 
 
+# What a convolution's backward needs from its forward (Engine._conv).  form: 'plain' (desc / info: the forward's descriptor and query
+# result, which the backward reuses), 'up2x' (payload: the four per-phase descriptors, under the arithmetic the forward ran on),
+# 'stem' (the space-to-depth form; its backward is the 7x7 weight gradient) or 'transpose' (payload: the virtual stride-2 convolution).
+# n_partials: rows of the BatchNorm statistics partials; fused: the inference epilogue ran (the output is the activation).
+ConvRecord = namedtuple('ConvRecord', 'form desc info n_partials payload fused')
+
+
 class _Tape(list):
     """The backward tape.  A closure recorded while the engine runs the depth branch on its own stream (Engine._branch_enter) replays
     on that stream too: the two encoder branches never read each other's gradients (the fusion's backward hands the depth branch its
@@ -204,13 +212,14 @@ class Engine(object):
         self.training = True
         self.plan = WeightPlan()   # batched weight transforms of a training step (off until the model enables it)
         self.kernel_log = None     # optional list collecting (layer, kernel_id) for profiling
-        self.up2x_wgrad_direct = os.environ.get('RCF_UP2X_WGRAD_DIRECT', '0') == '1'
+        # optional one-launch forms of the phase convolutions (Engine._one_launch); RCF_*_ONE_LAUNCH=0 switches one off
         self.up2x_wgrad_one_launch = os.environ.get('RCF_UP2X_WGRAD_ONE_LAUNCH', '1') != '0'
-        self._up2x_wgrad_ok = {}
         self.s2_dgrad_one_launch = os.environ.get('RCF_S2_DGRAD_ONE_LAUNCH', '1') != '0'
-        self._s2_dgrad_ok = {}
         self.s2_wgrad_one_launch = os.environ.get('RCF_S2_WGRAD_ONE_LAUNCH', '1') != '0'
-        self._s2_wgrad_ok = {}
+        # per-shape records of those forms (Engine._one_launch): {descriptor bytes: whether the library has the form for it}
+        self._up2x_wgrad_ok, self._s2_dgrad_ok, self._s2_wgrad_ok = {}, {}, {}
+        self._one_launch_ok = {'up2x': {}, 'up2x_wgrad': self._up2x_wgrad_ok, 's2_dgrad': self._s2_dgrad_ok, 's2_wgrad': self._s2_wgrad_ok,
+                               'pw_s2_dgrad': {}}
         # weight gradients on a side stream (fork after dZ is written, join before the optimizer / a gradient bucket's exchange): a
         # weight gradient is off the backward's critical path, and the BatchNorm-backward passes it then overlaps are HBM-bound kernels
         # that leave board power unused while the convolution kernels run AT the power limit
@@ -221,7 +230,6 @@ class Engine(object):
         self._side_keep = []
         self._open_switches = []       # stream switches entered and not yet left (recover() undoes them after an exception)
         self.pw_s2_dgrad_lowres = os.environ.get('RCF_PW_S2_DGRAD', '1') != '0'
-        self._pw_s2_ok = {}
         self.amax_chunk = 512          # slots per zero-filled chunk of the per-step maxima arena (two-plane fp16 arithmetic)
         self.amax_arena_cap = None     # tests only: never size the arena above this many slots
         self.completes_bucket = None   # callable(parameter) -> bool (data parallelism): this gradient finishes a bucket
@@ -238,7 +246,6 @@ class Engine(object):
         self.fuse_on_branch = os.environ.get('RCF_FUSE_ON_BRANCH', '1') != '0' and self.branch_stream
         self.fuse_wp_one_pass = os.environ.get('RCF_FUSE_WP_ONE_PASS', '1') != '0'   # inference: the fusion in one kernel (bf16 tensors)
         self.prof = None           # optional KernelTimer: brackets conv launches with events on the launch stream
-        self.use_phase_convs = True  # exact-2x UpConv and stride-2 dgrad as 2x2 phase convs (False: 9-tap / zero-insert forms)
         # the four forward phases of an up-2x conv in ONE launch (rcf_conv_desc.phase_sum == 2).  Round 5: the kernels stage x once per
         # channel chunk and run all four phases from that tile (bf16 tensors: conv_b16_kernel; fp32 tensors on two fp16 planes:
         # conv_split_kernel) -- a quarter of the loads (and, for fp32, of the plane conversions) of the four launches.  On for those two;
@@ -405,12 +412,8 @@ class Engine(object):
             return ops.phase_weights(w, mode)
         return e['out']
 
-    def _pack(self, desc, w, like, amax=None):
-        '''A packed-weight buffer holding ops.conv_pack(desc, w, ., amax).'''
-        return self._pack_n(desc, [w], like, amax)
-
     def _pack_n(self, desc, ws, like, amax=None):
-        '''len(ws) packings under one descriptor, back to back in one buffer (the four phases of a merged up-2x input gradient).
+        '''len(ws) packings under one descriptor, back to back in one buffer (one weight, or the four phases of a one-launch form).
         amax: the weights' maximum (two-plane fp16 descriptors on the split kernels), common to all of ws.'''
         plan = self.plan
         key = bytes(desc)
@@ -471,6 +474,17 @@ class Engine(object):
     @staticmethod
     def _shape(x):
         return (x.t if x.t is not None else x.z).shape
+
+    @staticmethod
+    def _grad_target(x, zero=False):
+        '''x.g for a kernel about to write x's gradient: the existing one is accumulated into (the BatchNorm-backward sums its first
+        writer left, Act.bsum, are stale then), else a new tensor shaped like x (zero-filled when zero=True).  -> accumulate'''
+        if x.g is not None:
+            x.bsum = None
+            return True
+        t = x.t if x.t is not None else x.z
+        x.g = torch.zeros_like(t) if zero else torch.empty_like(t)
+        return False
 
     def _side_enter(self, *keep):
         '''Switch to the side stream for a weight gradient (None when the switch is off).  keep: tensors the side-stream kernels read
@@ -577,9 +591,10 @@ class Engine(object):
                 self.on_param_grad(p)
 
     def _conv(self, layer, x, x2=None, up_hw=None, want_stats=False, fold=None):
-        '''conv (+ folded nearest-upsample of x to up_hw, + folded channel concat with x2) -> raw output z.
-        fold = (coef, res tensor or None): inference -- BatchNorm scale folded into the weights, bias + LeakyReLU (+ residual) in the
-        kernel's epilogue where it has one (info.fwd_act); the returned tensor is then the ACTIVATION and the 5th result True.'''
+        '''conv (+ folded nearest-upsample of x to up_hw, + folded channel concat with x2) -> (raw output z, ConvRecord, statistics
+        partials or None).  fold = (coef, res tensor or None): inference -- BatchNorm scale folded into the weights, bias + LeakyReLU
+        (+ residual) in the kernel's epilogue where it has one (info.fwd_act); the returned tensor is then the ACTIVATION and the
+        record's `fused` True.'''
         if x.s2d is not None and layer.kernel_size == 7 and layer.stride == 2 and x2 is None and up_hw is None:
             return self._conv_stem_s2d(layer, x, want_stats, fold)
         n, h, w, c1 = self._shape(x)
@@ -594,8 +609,8 @@ class Engine(object):
             if x2 is not None or up_hw is not None:
                 raise ValueError('a transposed convolution takes one source at its own resolution')
             return self._conv_transpose(layer, x, want_stats, fold)
-        if (self.use_phase_convs and gather == RCF_GATHER_NEAREST and x2 is None and layer.kernel_size == 3
-                and layer.stride == 1 and (h_in, w_in) == (2 * h, 2 * w) and c1 % 4 == 0):
+        if (gather == RCF_GATHER_NEAREST and x2 is None and layer.kernel_size == 3 and layer.stride == 1
+                and (h_in, w_in) == (2 * h, 2 * w) and c1 % 4 == 0):
             return self._conv_up2x(layer, x, want_stats, fold)
         desc = ops.make_fwd_desc(n, h_in, w_in, c1, c2, weight.shape[0], layer.kernel_size, layer.stride, h, w, gather)
         if desc.precision == RCF_PREC_F16X2:
@@ -613,55 +628,86 @@ class Engine(object):
             t1 = self._mat(x)
         if x2 is not None and t2 is None:
             t2 = self._mat(x2)
-        fused = fold is not None and info.fwd_act and k1 is None and k2 is None
-        scales = None
+        fused = bool(fold is not None and info.fwd_act and k1 is None and k2 is None)
+        packed = None
         if fused:
             def fold_pack():
                 buf = self._newf((info.packed_weight_floats,), t1)
                 ops.conv_pack(desc, ops.scale_channels(weight.detach(), fold[0][0]), buf)
                 return buf
             packed = self._frozen_get(('fold', id(layer), bytes(desc)), fold_pack)
-        elif self._two_plane(info.kernel_id):
-            wmax = self._w_amax(weight.detach())
-            packed = self._pack(desc, weight.detach(), t1, wmax)
-            scales = ops.make_scales(x.amax, None if x2 is None else x2.amax, wmax)
-        else:
-            packed = self._pack(desc, weight.detach(), t1)
         z = self._new((n, desc.h_out, desc.w_out, desc.c_out), t1)
         partials = torch.empty((info.n_partials, 2, desc.c_out), dtype=torch.float64, device=t1.device) if want_stats else None
-        if self.prof is not None:
-            self.prof.begin(info.kernel_id, ops.algorithmic_flops(desc), desc)
-        if fused:
-            ops.conv_fwd_act(desc, t1, t2, packed, fold[0][1], fold[1], z)
-        else:
-            ops.conv_fwd(desc, t1, t2, packed, z, partials, coef1=k1, coef2=k2, scales=scales)
-        if self.prof is not None:
-            self.prof.end()
-        if self.kernel_log is not None and desc is not None:
+        self._fwd_launch(desc, weight.detach(), t1, z, in2=t2, info=info, packed=packed, amax_in=x.amax,
+                         amax_in2=None if x2 is None else x2.amax, partials=partials, coef1=k1, coef2=k2,
+                         bias=fold[0][1] if fused else None, res=fold[1] if fused else None)
+        if self.kernel_log is not None:
             self.kernel_log.append((desc.ksize, desc.stride, desc.c1 + desc.c2, desc.c_out, desc.h_out, desc.w_out,
                                     info.kernel_id))
-        if fold is not None:
-            return z, desc, info, partials, fused
-        return z, desc, info, partials
+        return z, ConvRecord('plain', desc, info, info.n_partials, None, fused), partials
 
-    def _run_packed(self, desc, w_oihw, in1, out, partials=None, coef1=None, bias=None, amax_in=None, amax_w=None):
-        '''amax_in / amax_w: the maxima of in1 and of the weight BUFFER w_oihw is a slice of (two-plane fp16 descriptors; the
-        caller has put the descriptor on the exact arithmetic when one of them is unknown).'''
-        info = ops.conv_query(desc)
-        scales = None
-        if self._two_plane(info.kernel_id):
-            packed = self._pack(desc, w_oihw, in1, amax_w)
-            scales = ops.make_scales(amax_in, None, amax_w)
-        else:
-            packed = self._pack(desc, w_oihw, in1)
+    def _fwd_launch(self, desc, w, in1, out, in2=None, phase=None, info=None, packed=None, wmax=None, amax_in=None, amax_in2=None,
+                    partials=None, coef1=None, coef2=None, bias=None, res=None, sums_for=None, flops=None):
+        '''The launch of every forward-form convolution -- a forward, an input gradient, one phase or all four phases of a phase form:
+        queries desc (unless the caller passes its info), packs the weights, brackets prof and launches.  Returns the info.
+        w: the OIHW weight, or a phase-weight buffer [4][O'][I'][2][2] of which `phase` selects one (None: all four, packed back to back
+        under the one descriptor).  packed (+ wmax): weights the caller has packed itself (folded inference weights, the stems).
+        On a two-plane fp16 kernel the weights are packed with max|w| (of the whole buffer: the four phases share one maximum) and the
+        scales take the operands' maxima by role: amax_in (in1), amax_in2 (in2), the weights'.  The caller has put the descriptor on the
+        exact arithmetic when one of them is unknown (_exact_unless).
+        bias (+ res): the inference epilogue (conv_fwd_act).  sums_for: the Act whose gradient this input-gradient launch writes first;
+        the kernel also takes its BatchNorm-backward sums where it can (_bn_sums_launch).'''
+        if info is None:
+            info = ops.conv_query(desc)
+        two_plane = self._two_plane(info.kernel_id)
+        if packed is None:
+            wmax = self._w_amax(w) if two_plane else None
+            packed = self._pack_n(desc, [w] if w.dim() == 4 else (list(w) if phase is None else [w[phase]]), in1, wmax)
+        scales = ops.make_scales(amax_in, amax_in2, wmax) if two_plane else None
         if self.prof is not None:
-            self.prof.begin(info.kernel_id, ops.algorithmic_flops(desc), desc)
+            self.prof.begin(info.kernel_id, ops.algorithmic_flops(desc) if flops is None else flops, desc)
         if bias is not None:
-            ops.conv_fwd_act(desc, in1, None, packed, bias, None, out)
-        else:
-            ops.conv_fwd(desc, in1, None, packed, out, partials, coef1=coef1, scales=scales)
+            ops.conv_fwd_act(desc, in1, in2, packed, bias, res, out)
+        elif not self._bn_sums_launch(desc, info, in1, packed, out, scales, sums_for):
+            ops.conv_fwd(desc, in1, in2, packed, out, partials, coef1=coef1, coef2=coef2, scales=scales)
         if self.prof is not None:
             self.prof.end()
+        return info
+
+    def _wgrad_launch(self, desc, in1, dz, dw, in2=None, info=None, amax_in=None, amax_in2=None, amax_dz=None, coef1=None, coef2=None):
+        '''The launch of every weight gradient: dw of the convolution desc from its operands in1 (+ in2) and its output gradient dz;
+        queries desc unless the caller passes its info, allocates the workspace, brackets prof.  On a two-plane fp16 kernel the scales
+        take the operands' maxima by role: amax_in (in1), amax_in2 (in2), amax_dz (dz).'''
+        if info is None:
+            info = ops.conv_query(desc)
+        ws = self._newf((max(1, info.wgrad_workspace_floats),), dz)
+        scales = ops.make_scales(amax_in, amax_in2, None, amax_dz) if self._two_plane_wgrad(info.wgrad_kernel_id) else None
+        if self.prof is not None:
+            self.prof.begin(info.wgrad_kernel_id, ops.algorithmic_flops(desc), desc)
+        try:
+            ops.conv_wgrad(desc, in1, in2, dz, dw, ws, coef1=coef1, coef2=coef2, scales=scales)
+        finally:   # (the library may refuse a one-launch form only here: Engine._one_launch then runs the per-phase launches)
+            if self.prof is not None:
+                self.prof.end()
+
+    def _one_launch(self, form, on, desc, launch=None):
+        '''The query info of an optional one-launch form, or None: its switch `on` is off, or the library has no kernel for desc
+        (remembered per form and shape) -- the caller then runs the per-phase launches.  launch(info): the form's launch, run here
+        when given (a weight-gradient form may be refused at its launch).'''
+        if not on:
+            return None
+        memo = self._one_launch_ok[form]
+        key = bytes(desc)
+        if memo.get(key) is False:
+            return None
+        try:
+            info = ops.conv_query(desc)
+            if launch is not None:
+                launch(info)
+        except ops._lib.RcfUnsupported:   # no kernel for this form (any other error -- a launch failure -- propagates)
+            memo[key] = False
+            return None
+        memo[key] = True
         return info
 
     def _conv_up2x(self, layer, x, want_stats, fold=None):
@@ -672,102 +718,36 @@ class Engine(object):
         n, h, w, c1 = self._shape(x)
         weight = layer.conv.weight
         co = weight.shape[0]
-        descs, partials, n_part = [], None, 0
-        t1 = k1 = z = wmax = None
-        fused = False
-        f16 = self._f16()
-        if f16:
+        if self._f16():
             self._mat(x)   # two fp16 planes need max|x|: a deferred activation is materialised (its producer pass supplies it)
+        w_known = None if fold is not None else 0   # (the folded inference weights have no maximum: exact arithmetic)
+        # the backward pass's per-phase descriptors, under the arithmetic the forward runs on
+        phases = [self._exact_unless(ops.make_up2x_fwd_desc(n, h, w, c1, co, ph >> 1, ph & 1), x.amax, w_known) for ph in range(4)]
         # the four phases in ONE launch (rcf_conv_desc.phase_sum == 2) where the layer runs on a split / DMA kernel: a workgroup runs the
         # four 2x2 convolutions of its tile back to back, so x comes from HBM once (the three re-reads hit L2) and three launches go;
         # the backward pass keeps the four per-phase descriptors (their weight gradients are four launches)
-        if self.up2x_one_launch is not False:
-            dm = ops.make_up2x_fwd_desc(n, h, w, c1, co, 0, 0, phase_out=True)
-            if f16:
-                dm = self._exact_unless(dm, x.amax, None if fold is not None else 0)
-            qm = None
-            if self.up2x_one_launch or ops.act_dtype() == torch.bfloat16 or dm.precision == RCF_PREC_F16X2:
-                try:
-                    qm = ops.conv_query(dm)
-                except ops._lib.RcfUnsupported:   # no kernel for this form (any other error -- a launch failure -- propagates)
-                    qm = None
-            if qm is not None:
-                return self._conv_up2x_merged(layer, x, dm, qm, want_stats, fold)
-        for ph in range(4):
-            d = ops.make_up2x_fwd_desc(n, h, w, c1, co, ph >> 1, ph & 1)
-            if f16:
-                d = self._exact_unless(d, x.amax, None if fold is not None else 0)
-            if ph == 0:
-                qi = ops.conv_query(d)
-                n_part = qi.n_partials
-                fused = fold is not None and bool(qi.fwd_act) and fold[1] is None
-                wp = self._frozen_get(('fold-phase', id(layer)), lambda: ops.phase_weights(ops.scale_channels(weight.detach(), fold[0][0]),
-                                                                                              RCF_PHASE_UP2X_FWD)) if fused else \
-                    self._phase_w(weight.detach(), RCF_PHASE_UP2X_FWD)
-                if self._two_plane(qi.kernel_id):
-                    wmax = self._w_amax(wp)   # one maximum for the four phases' pre-summed weights
-                t1, k1 = self._src(x, qi.bn_on_load and not fused)
-                if t1 is None:
-                    t1 = self._mat(x)
-                z = self._new((n, 2 * h, 2 * w, co), t1)
-                if want_stats:
-                    partials = torch.empty((4 * n_part, 2, co), dtype=torch.float64, device=t1.device)
-            self._run_packed(d, wp[ph], t1, z, None if partials is None else partials[ph * n_part:(ph + 1) * n_part], coef1=k1,
-                             bias=fold[0][1] if fused else None, amax_in=x.amax, amax_w=wmax)
-            descs.append(d)
-
-        class _Info(object):
-            pass
-        info = _Info()
-        info.n_partials = 4 * n_part
-        info.up2x = descs
-        if fold is not None:
-            return z, None, info, partials, fused
-        return z, None, info, partials
-
-    def _conv_up2x_merged(self, layer, x, dm, qm, want_stats, fold):
-        '''The up-2x forward as one launch over the four output phases (see _conv_up2x); returns what _conv_up2x returns.'''
-        n, h, w, c1 = self._shape(x)
-        weight = layer.conv.weight
-        co = weight.shape[0]
-        fused = fold is not None and bool(qm.fwd_act) and fold[1] is None
+        dm = self._exact_unless(ops.make_up2x_fwd_desc(n, h, w, c1, co, 0, 0, phase_out=True), x.amax, w_known)
+        on = self.up2x_one_launch is not False and (self.up2x_one_launch or ops.act_dtype() == torch.bfloat16
+                                                    or dm.precision == RCF_PREC_F16X2)
+        info = self._one_launch('up2x', on, dm)
+        launches = phases if info is None else [dm]
+        if info is None:
+            info = ops.conv_query(phases[0])
+        n_part = info.n_partials
+        fused = fold is not None and bool(info.fwd_act) and fold[1] is None
         wp = self._frozen_get(('fold-phase', id(layer)), lambda: ops.phase_weights(ops.scale_channels(weight.detach(), fold[0][0]),
                                                                                       RCF_PHASE_UP2X_FWD)) if fused else \
             self._phase_w(weight.detach(), RCF_PHASE_UP2X_FWD)
-        t1, k1 = self._src(x, qm.bn_on_load and not fused)
+        t1, k1 = self._src(x, info.bn_on_load and not fused)
         if t1 is None:
             t1 = self._mat(x)
-        scales = None
-        if self._two_plane(qm.kernel_id):
-            wmax = self._w_amax(wp)   # one maximum for the four phases' pre-summed weights
-            packed = self._pack_n(dm, [wp[ph] for ph in range(4)], t1, wmax)
-            scales = ops.make_scales(x.amax, None, wmax)
-        else:
-            packed = self._pack_n(dm, [wp[ph] for ph in range(4)], t1)
         z = self._new((n, 2 * h, 2 * w, co), t1)
-        partials = torch.empty((qm.n_partials, 2, co), dtype=torch.float64, device=t1.device) if want_stats else None
-        if self.prof is not None:
-            self.prof.begin(qm.kernel_id, ops.algorithmic_flops(dm), dm)
-        if fused:
-            ops.conv_fwd_act(dm, t1, None, packed, fold[0][1], None, z)
-        else:
-            ops.conv_fwd(dm, t1, None, packed, z, partials, coef1=k1, scales=scales)
-        if self.prof is not None:
-            self.prof.end()
-        descs = []
-        for ph in range(4):   # the backward pass's per-phase descriptors, under the arithmetic the forward ran on
-            d = ops.make_up2x_fwd_desc(n, h, w, c1, co, ph >> 1, ph & 1)
-            d.precision = dm.precision
-            descs.append(d)
-
-        class _Info(object):
-            pass
-        info = _Info()
-        info.n_partials = qm.n_partials
-        info.up2x = descs
-        if fold is not None:
-            return z, None, info, partials, fused
-        return z, None, info, partials
+        partials = torch.empty((len(launches) * n_part, 2, co), dtype=torch.float64, device=t1.device) if want_stats else None
+        for ph, d in enumerate(launches):
+            self._fwd_launch(d, wp, t1, z, phase=None if d is dm else ph, info=info if ph == 0 else None,
+                             partials=None if partials is None else partials[ph * n_part:(ph + 1) * n_part], coef1=k1,
+                             bias=fold[0][1] if fused else None, amax_in=x.amax)
+        return z, ConvRecord('up2x', launches[0], info, len(launches) * n_part, phases, fused), partials
 
     def _conv_stem_s2d(self, layer, x, want_stats, fold=None):
         '''
@@ -785,11 +765,13 @@ class Engine(object):
         d = ops.make_stem_s2d_desc(n, h, w, co, f32=f32)
         info = ops.conv_query(d)
         fused = fold is not None and bool(info.fwd_act) and fold[1] is None
+        if fused and f32:
+            raise RuntimeError('the fp32 stem has no fused inference epilogue on two planes')   # fold -> exact arithmetic upstream
 
         def stem_weights():
             return ops.stem_weights_s2d(ops.scale_channels(weight.detach(), fold[0][0]) if fused else weight.detach())
 
-        scales = None
+        wmax = None
         if f32:
             # two fp16 planes: the 4x4 weights' maximum is computed on the transformed tensor (one small launch; the stems are two layers)
             def stem_pack32():
@@ -799,7 +781,6 @@ class Engine(object):
                 ops.conv_pack(d, w4, buf, wmax)
                 return buf, wmax
             packed, wmax = self._frozen_get(('stem32', id(layer), bool(fused)), stem_pack32)
-            scales = ops.make_scales(x.amax, None, wmax)
         else:
             def stem_pack():
                 buf = self._newf((info.packed_weight_floats,), x.s2d)
@@ -808,25 +789,10 @@ class Engine(object):
             packed = self._frozen_get(('stem', id(layer), bool(fused)), stem_pack)
         z = torch.empty((n, d.h_out, d.w_out, co), dtype=x.s2d.dtype, device=x.s2d.device)
         partials = torch.empty((info.n_partials, 2, co), dtype=torch.float64, device=z.device) if want_stats else None
-        if self.prof is not None:
-            self.prof.begin(info.kernel_id, 2.0 * n * d.h_out * d.w_out * co * 49 * x.t.shape[3] if x.t is not None else 0.0, d)
-        if fused:
-            if f32:
-                raise RuntimeError('the fp32 stem has no fused inference epilogue on two planes')   # fold -> exact arithmetic upstream
-            ops.conv_fwd_act(d, x.s2d, None, packed, fold[0][1], None, z)
-        else:
-            ops.conv_fwd(d, x.s2d, None, packed, z, partials, scales=scales)
-        if self.prof is not None:
-            self.prof.end()
-
-        class _Info(object):
-            pass
-        sinfo = _Info()
-        sinfo.n_partials = info.n_partials
-        sinfo.stem = True
-        if fold is not None:
-            return z, None, sinfo, partials, fused
-        return z, None, sinfo, partials
+        self._fwd_launch(d, None, x.s2d, z, info=info, packed=packed, wmax=wmax, amax_in=x.amax, partials=partials,
+                         bias=fold[0][1] if fused else None,
+                         flops=2.0 * n * d.h_out * d.w_out * co * 49 * x.t.shape[3] if x.t is not None else 0.0)
+        return z, ConvRecord('stem', d, info, info.n_partials, None, fused), partials
 
     def _conv_transpose(self, layer, x, want_stats, fold=None):
         '''
@@ -844,145 +810,29 @@ class Engine(object):
         t1 = self._mat(x)
         wd = self._phase_w(weight.detach(), RCF_PHASE_S2_DGRAD)
         z = self._new((n, 2 * h, 2 * w, co), t1)
-        partials, n_part, wmax = None, 0, None
-        for ph in range(4):
-            d = self._exact_unless(ops.make_s2_dgrad_desc(virt, ph >> 1, ph & 1, False), x.amax)
-            if ph == 0:
-                qi = ops.conv_query(d)
-                n_part = qi.n_partials
-                if self._two_plane(qi.kernel_id):
-                    wmax = self._w_amax(wd)
-                if want_stats:
-                    partials = torch.empty((4 * n_part, 2, co), dtype=torch.float64, device=t1.device)
-            self._run_packed(d, wd[ph], t1, z, None if partials is None else partials[ph * n_part:(ph + 1) * n_part],
-                             amax_in=x.amax, amax_w=wmax)
+        phases = [self._exact_unless(ops.make_s2_dgrad_desc(virt, ph >> 1, ph & 1, False), x.amax) for ph in range(4)]
+        info = ops.conv_query(phases[0])
+        n_part = info.n_partials
+        partials = torch.empty((4 * n_part, 2, co), dtype=torch.float64, device=t1.device) if want_stats else None
+        for ph, d in enumerate(phases):
+            self._fwd_launch(d, wd, t1, z, phase=ph, info=info if ph == 0 else None,
+                             partials=None if partials is None else partials[ph * n_part:(ph + 1) * n_part], amax_in=x.amax)
+        return z, ConvRecord('transpose', phases[0], info, 4 * n_part, virt, False), partials
 
-        class _Info(object):
-            pass
-        info = _Info()
-        info.n_partials = 4 * n_part
-        info.transpose = virt
-        if fold is not None:
-            return z, None, info, partials, False
-        return z, None, info, partials
-
-    def _conv_transpose_backward(self, layer, info, x, dz, dz_amax=None):
+    def _conv_transpose_backward(self, layer, rec, x, dz, dz_amax=None):
         '''dW = the weight gradient of the virtual stride-2 convolution with the roles swapped (its input is dY, its output
         gradient is x) -- already in the [in][out][3][3] layout of ConvTranspose2d.weight; dX = that convolution applied to dY.'''
-        virt = self._exact_unless(info.transpose, dz_amax, x.amax)
+        virt = self._exact_unless(rec.payload, dz_amax, x.amax)
         weight = layer.conv.weight
-        qi = ops.conv_query(virt)
-        ws = self._newf((max(1, qi.wgrad_workspace_floats),), dz)
-        scales = ops.make_scales(dz_amax, None, None, x.amax) if self._two_plane_wgrad(qi.wgrad_kernel_id) else None
-        if self.prof is not None:
-            self.prof.begin(qi.wgrad_kernel_id, ops.algorithmic_flops(virt), virt)
-        ops.conv_wgrad(virt, dz, None, self._mat(x), self.grad_of(weight), ws, scales=scales)
-        if self.prof is not None:
-            self.prof.end()
+        self._wgrad_launch(virt, dz, self._mat(x), self.grad_of(weight), amax_in=dz_amax, amax_dz=x.amax)   # (the roles swapped)
         self._wgrad_done(weight)
         if x.needs_grad:
-            acc = x.g is not None
-            if acc:
-                x.bsum = None
-            if not acc:
-                x.g = self._new(tuple(self._shape(x)), dz)
+            acc = self._grad_target(x)
             dd = ops.make_fwd_desc(virt.n, virt.h_in, virt.w_in, virt.c1, 0, virt.c_out, 3, 2)
             dd.accumulate = 1 if acc else 0
-            dd = self._exact_unless(dd, dz_amax)
-            wmax = self._w_amax(weight.detach()) if self._two_plane(ops.conv_query(dd).kernel_id) else None
-            self._run_packed(dd, weight.detach(), dz, x.g, amax_in=dz_amax, amax_w=wmax)
+            self._fwd_launch(self._exact_unless(dd, dz_amax), weight.detach(), dz, x.g, amax_in=dz_amax)
 
-    def _s2_dgrad_merged(self, fwd, wd, dz, dx, acc, dz_amax):
-        '''The input gradient of a 3x3 stride-2 convolution as ONE launch over its four output phases (rcf_conv_desc.phase_sum == 3: dz
-        staged once per channel chunk, only the 1 + 2 + 2 + 4 taps that exist -- the four per-phase launches multiply the other seven
-        by zero weights).  bf16 tensors and fp32 tensors on two fp16 planes; returns False elsewhere (remembered per shape) and the
-        caller runs the four launches.  RCF_S2_DGRAD_ONE_LAUNCH=0 switches it off.'''
-        if not self.s2_dgrad_one_launch:
-            return False
-        dm = self._exact_unless(ops.make_s2_dgrad_desc(fwd, 0, 0, acc, phase_out=True), dz_amax)
-        key = bytes(dm)
-        if self._s2_dgrad_ok.get(key) is False:
-            return False
-        try:
-            qm = ops.conv_query(dm)
-        except ops._lib.RcfUnsupported:   # no kernel for this form (any other error -- a launch failure -- propagates)
-            self._s2_dgrad_ok[key] = False
-            return False
-        self._s2_dgrad_ok[key] = True
-        scales = None
-        if self._two_plane(qm.kernel_id):
-            wmax = self._w_amax(wd)
-            packed = self._pack_n(dm, [wd[ph] for ph in range(4)], dz, wmax)
-            scales = ops.make_scales(dz_amax, None, wmax)
-        else:
-            packed = self._pack_n(dm, [wd[ph] for ph in range(4)], dz)
-        if self.prof is not None:
-            self.prof.begin(qm.kernel_id, ops.algorithmic_flops(dm), dm)
-        ops.conv_fwd(dm, dz, None, packed, dx, None, scales=scales)
-        if self.prof is not None:
-            self.prof.end()
-        return True
-
-    def _s2_wgrad_merged(self, fwd, t1, dz, dwp, x_amax, dz_amax):
-        '''The four phase weight gradients of a 3x3 stride-2 convolution from ONE launch (rcf_conv2d_wgrad on the phase_sum == 1
-        descriptor; the four phases of a tile share an XCD and with it the dz tile).  False where the library has no such launch
-        (remembered per shape): the caller runs the four per-phase calls.  RCF_S2_WGRAD_ONE_LAUNCH=0 switches it off.'''
-        if not self.s2_wgrad_one_launch:
-            return False
-        dm = self._exact_unless(ops.make_s2_wgrad_desc(fwd, 0, 0, all_phases=True), x_amax, dz_amax)
-        key = bytes(dm)
-        if self._s2_wgrad_ok.get(key) is False:
-            return False
-        try:
-            qm = ops.conv_query(dm)
-            ws = self._newf((max(1, qm.wgrad_workspace_floats),), dz)
-            scales = ops.make_scales(x_amax, None, None, dz_amax) if self._two_plane_wgrad(qm.wgrad_kernel_id) else None
-            if self.prof is not None:
-                self.prof.begin(qm.wgrad_kernel_id, 4.0 * ops.algorithmic_flops(ops.make_s2_wgrad_desc(fwd, 0, 0)), dm)
-            try:
-                ops.conv_wgrad(dm, t1, None, dz, dwp, ws, scales=scales)
-            finally:
-                if self.prof is not None:
-                    self.prof.end()
-        except ops._lib.RcfUnsupported:   # no kernel for this form (any other error -- a launch failure -- propagates)
-            self._s2_wgrad_ok[key] = False
-            return False
-        self._s2_wgrad_ok[key] = True
-        return True
-
-    def _up2x_wgrad_merged(self, info, x, dz, dz_amax, dwp):
-        '''The four phase weight gradients of an up-2x convolution from ONE launch (rcf_conv2d_wgrad on the phase_sum == 2 descriptor:
-        split weight-gradient kernels only; the four phases of a tile share an XCD, so x is fetched from HBM once).  Returns False where
-        the library has no such launch for this layer (remembered per shape) -- the caller then runs the four per-phase calls.
-        RCF_UP2X_WGRAD_ONE_LAUNCH=0 switches it off.'''
-        if not self.up2x_wgrad_one_launch or self.bn_on_load:   # (BatchNorm-on-load sources keep the per-phase calls)
-            return False
-        n, h, w, c1 = self._shape(x)
-        co = dwp.shape[1]
-        d0 = self._exact_unless(info.up2x[0], x.amax, dz_amax)
-        key = (n, h, w, c1, co, d0.precision, d0.storage)
-        if self._up2x_wgrad_ok.get(key) is False:
-            return False
-        dm = ops.make_up2x_fwd_desc(n, h, w, c1, co, 0, 0, phase_out=True)
-        dm.precision = d0.precision
-        try:
-            qm = ops.conv_query(dm)
-            ws = self._newf((max(1, qm.wgrad_workspace_floats),), dz)
-            scales = ops.make_scales(x.amax, None, None, dz_amax) if self._two_plane_wgrad(qm.wgrad_kernel_id) else None
-            if self.prof is not None:
-                self.prof.begin(qm.wgrad_kernel_id, 4.0 * ops.algorithmic_flops(info.up2x[0]), dm)
-            try:
-                ops.conv_wgrad(dm, self._mat(x), None, dz, dwp, ws, scales=scales)
-            finally:
-                if self.prof is not None:
-                    self.prof.end()
-        except ops._lib.RcfUnsupported:   # no kernel for this form (any other error -- a launch failure -- propagates)
-            self._up2x_wgrad_ok[key] = False
-            return False
-        self._up2x_wgrad_ok[key] = True
-        return True
-
-    def _conv_up2x_backward(self, layer, info, x, dz, dz_amax=None):
+    def _conv_up2x_backward(self, layer, rec, x, dz, dz_amax=None):
         n, h, w, c1 = self._shape(x)
         weight = layer.conv.weight
         co = weight.shape[0]
@@ -990,191 +840,124 @@ class Engine(object):
         if self.wgrad_side and not self.bn_on_load:
             self._mat(x)
             side = self._side_enter(dz, x.t)
-        if self.up2x_wgrad_direct:
-            # A/B switch (RCF_UP2X_WGRAD_DIRECT=1): the weight gradient as ONE 3x3 weight gradient at the upsampled resolution with the
-            # nearest gather (2.25x the MFMA work of the four 2x2 phases, x and dz staged once) -- measured, not faster: DESIGN Appendix A
-            d3 = self._exact_unless(ops.make_fwd_desc(n, 2 * h, 2 * w, c1, 0, co, 3, 1, h, w, RCF_GATHER_NEAREST), x.amax, dz_amax)
-            q3 = ops.conv_query(d3)
-            ws = self._newf((max(1, q3.wgrad_workspace_floats),), dz)
-            scales = ops.make_scales(x.amax, None, None, dz_amax) if self._two_plane_wgrad(q3.wgrad_kernel_id) else None
-            ops.conv_wgrad(d3, self._mat(x), None, dz, self.grad_of(weight), ws, scales=scales)
-            info = None
-        dwp = self._newf((4, co, c1, 2, 2), dz) if info is not None else None
-        if info is not None and self._up2x_wgrad_merged(info, x, dz, dz_amax, dwp):
-            info = None   # the four phases' weight gradients came from one launch
-        for ph, d in enumerate(info.up2x if info is not None else ()):
-            d = self._exact_unless(d, x.amax, dz_amax)
-            qi = ops.conv_query(d)
-            ws = self._newf((max(1, qi.wgrad_workspace_floats),), dz)
-            t1, k1 = self._src(x, qi.wgrad_bn_on_load)
-            if t1 is None:
-                t1 = self._mat(x)
-            scales = ops.make_scales(x.amax, None, None, dz_amax) if self._two_plane_wgrad(qi.wgrad_kernel_id) else None
-            if self.prof is not None:
-                self.prof.begin(qi.wgrad_kernel_id, ops.algorithmic_flops(d), d)
-            ops.conv_wgrad(d, t1, None, dz, dwp[ph], ws, coef1=k1, scales=scales)
-            if self.prof is not None:
-                self.prof.end()
-        if dwp is not None:
-            ops.phase_wgrad_fold(dwp, self.grad_of(weight))
+        dwp = self._newf((4, co, c1, 2, 2), dz)
+        # the four phase weight gradients from ONE launch where the library has it (rcf_conv2d_wgrad on the phase_sum == 2 descriptor:
+        # split weight-gradient kernels only; the four phases of a tile share an XCD, so x is fetched from HBM once), else four.
+        # RCF_UP2X_WGRAD_ONE_LAUNCH=0 switches it off; BatchNorm-on-load sources keep the per-phase calls
+        dm = ops.make_up2x_fwd_desc(n, h, w, c1, co, 0, 0, phase_out=True)
+        dm.precision = self._exact_unless(rec.payload[0], x.amax, dz_amax).precision
+        if self._one_launch('up2x_wgrad', self.up2x_wgrad_one_launch and not self.bn_on_load, dm,
+                            lambda info: self._wgrad_launch(dm, self._mat(x), dz, dwp, info=info, amax_in=x.amax, amax_dz=dz_amax)) is None:
+            for ph, d in enumerate(rec.payload):
+                d = self._exact_unless(d, x.amax, dz_amax)
+                info = ops.conv_query(d)
+                t1, k1 = self._src(x, info.wgrad_bn_on_load)
+                self._wgrad_launch(d, self._mat(x) if t1 is None else t1, dz, dwp[ph], info=info, amax_in=x.amax, amax_dz=dz_amax,
+                                   coef1=k1)
+        ops.phase_wgrad_fold(dwp, self.grad_of(weight))
         self._side_exit(side)
         self._wgrad_done(weight)
         if x.needs_grad:
             wd = self._phase_w(weight.detach(), RCF_PHASE_UP2X_DGRAD)
-            acc = x.g is not None
-            if acc:
-                x.bsum = None
-            if not acc:
-                x.g = self._new(tuple(self._shape(x)), dz)
+            acc = self._grad_target(x)
             dd = self._exact_unless(ops.make_up2x_dgrad_desc(n, h, w, c1, co, 0, 0, acc, phase_sum=True), dz_amax)
-            qi = ops.conv_query(dd)
-            scales = None
-            if self._two_plane(qi.kernel_id):
-                wmax = self._w_amax(wd)
-                packed = self._pack_n(dd, [wd[ph] for ph in range(4)], dz, wmax)
-                scales = ops.make_scales(dz_amax, None, wmax)
-            else:
-                packed = self._pack_n(dd, [wd[ph] for ph in range(4)], dz)
-            if self.prof is not None:
-                self.prof.begin(qi.kernel_id, ops.algorithmic_flops(dd), dd)
-            if not self._bn_sums_launch(dd, qi, dz, packed, x.g, scales, None if acc else x):
-                ops.conv_fwd(dd, dz, None, packed, x.g, None, scales=scales)
-            if self.prof is not None:
-                self.prof.end()
+            self._fwd_launch(dd, wd, dz, x.g, amax_in=dz_amax, sums_for=None if acc else x)
 
-    def _conv_backward(self, layer, desc, info, x, x2, dz, dz_amax=None):
-        '''dW (written once into the parameter's gradient) and dX / dX2 (accumulated into the producers' .g).  dz_amax: device
-        scalar with max|dz| from the kernel that wrote dz (two-plane fp16 arithmetic; None: these layers run exact).'''
-        if desc is None and hasattr(info, 'stem'):
+    def _conv_backward(self, layer, rec, x, x2, dz, dz_amax=None):
+        '''dW (written once into the parameter's gradient) and dX / dX2 (accumulated into the producers' .g).  rec: the forward's
+        ConvRecord.  dz_amax: device scalar with max|dz| from the kernel that wrote dz (two-plane fp16 arithmetic; None: these layers
+        run exact).'''
+        if rec.form == 'transpose':
+            return self._conv_transpose_backward(layer, rec, x, dz, dz_amax)
+        if rec.form == 'up2x':
+            return self._conv_up2x_backward(layer, rec, x, dz, dz_amax)
+        desc, info = rec.desc, rec.info
+        if rec.form == 'stem':
             # the stem ran on the space-to-depth image; its weight gradient is the 7x7 one on the fp32 NHWC input (no input gradient)
             n, h, w, c = x.t.shape
             desc = ops.make_fwd_desc(n, h, w, c, 0, layer.conv.weight.shape[0], 7, 2)
             info = ops.conv_query(desc)
-        if desc is None and hasattr(info, 'transpose'):
-            return self._conv_transpose_backward(layer, info, x, dz, dz_amax)
-        if desc is None:
-            return self._conv_up2x_backward(layer, info, x, dz, dz_amax)
         weight = layer.conv.weight
         dw = self.grad_of(weight)
         x_amax = x.amax
         x2_amax = 0 if x2 is None else x2.amax
-        s2_phases = self.s2_wgrad_phases if self.s2_wgrad_phases is not None else (ops.act_dtype() == torch.bfloat16 or ops.get_precision() == 2)
+        s2_phases = self.s2_wgrad_phases if self.s2_wgrad_phases is not None else (ops.act_dtype() == torch.bfloat16 or
+                                                                                    ops.get_precision() == RCF_PREC_F16X2)
         side = None
         if self.wgrad_side and not self.bn_on_load:
             self._mat(x)
             if x2 is not None:
                 self._mat(x2)
             side = self._side_enter(dz, x.t, None if x2 is None else x2.t)
-        if (self.use_phase_convs and s2_phases and desc.stride == 2 and desc.ksize == 3 and x2 is None and desc.c1 % 4 == 0
-                and desc.c1 >= 16 and desc.gather1 == RCF_GATHER_DIRECT):
-            # 3x3 stride-2 weight gradient as four 2x2 weight gradients on the phase images of x (bf16 matrix pipe)
+        if (s2_phases and desc.stride == 2 and desc.ksize == 3 and x2 is None and desc.c1 % 4 == 0 and desc.c1 >= 16
+                and desc.gather1 == RCF_GATHER_DIRECT):
+            # 3x3 stride-2 weight gradient as four 2x2 weight gradients on the phase images of x (bf16 matrix pipe): from ONE launch
+            # where the library has it (rcf_conv2d_wgrad on the phase_sum == 1 descriptor; the four phases of a tile share an XCD and
+            # with it the dz tile), else four.  RCF_S2_WGRAD_ONE_LAUNCH=0 switches the one launch off
             t1 = self._mat(x)
             dwp = self._newf((4, desc.c_out, desc.c1, 2, 2), dz)
-            for ph in (() if self._s2_wgrad_merged(desc, t1, dz, dwp, x_amax, dz_amax) else range(4)):
-                d = self._exact_unless(ops.make_s2_wgrad_desc(desc, ph >> 1, ph & 1), x_amax, dz_amax)
-                qi = ops.conv_query(d)
-                wsp = self._newf((max(1, qi.wgrad_workspace_floats),), dz)
-                scales = ops.make_scales(x_amax, None, None, dz_amax) if self._two_plane_wgrad(qi.wgrad_kernel_id) else None
-                if self.prof is not None:
-                    self.prof.begin(qi.wgrad_kernel_id, ops.algorithmic_flops(d), d)
-                ops.conv_wgrad(d, t1, None, dz, dwp[ph], wsp, scales=scales)
-                if self.prof is not None:
-                    self.prof.end()
+            dm = self._exact_unless(ops.make_s2_wgrad_desc(desc, 0, 0, all_phases=True), x_amax, dz_amax)
+            if self._one_launch('s2_wgrad', self.s2_wgrad_one_launch, dm,
+                                lambda info: self._wgrad_launch(dm, t1, dz, dwp, info=info, amax_in=x_amax, amax_dz=dz_amax)) is None:
+                for ph in range(4):
+                    d = self._exact_unless(ops.make_s2_wgrad_desc(desc, ph >> 1, ph & 1), x_amax, dz_amax)
+                    self._wgrad_launch(d, t1, dz, dwp[ph], amax_in=x_amax, amax_dz=dz_amax)
             ops.phase_wgrad_gather_s2(dwp, dw)
         else:
             wdesc, winfo = desc, info
             if desc.precision == RCF_PREC_F16X2 and (dz_amax is None or x_amax is None or x2_amax is None):
                 wdesc = self._exact_unless(desc, None)
                 winfo = ops.conv_query(wdesc)
-            ws = self._newf((max(1, winfo.wgrad_workspace_floats),), dz)
-            if self.prof is not None:
-                self.prof.begin(winfo.wgrad_kernel_id, ops.algorithmic_flops(wdesc), wdesc)
             t1, k1 = self._src(x, winfo.wgrad_bn_on_load)
             t2, k2 = self._src(x2, winfo.wgrad_bn_on_load)
             if t1 is None:
                 t1 = self._mat(x)
             if x2 is not None and t2 is None:
                 t2 = self._mat(x2)
-            scales = None
-            if self._two_plane_wgrad(winfo.wgrad_kernel_id):
-                scales = ops.make_scales(x_amax, None if x2 is None else x2_amax, None, dz_amax)
-            ops.conv_wgrad(wdesc, t1, t2, dz, dw, ws, coef1=k1, coef2=k2, scales=scales)
-            if self.prof is not None:
-                self.prof.end()
+            self._wgrad_launch(wdesc, t1, dz, dw, in2=t2, info=winfo, amax_in=x_amax, amax_in2=None if x2 is None else x2_amax,
+                               amax_dz=dz_amax, coef1=k1, coef2=k2)
         self._side_exit(side)
         self._wgrad_done(weight)
         for src, off, cnt in ((x, 0, desc.c1), (x2, desc.c1, desc.c2)):
             if src is None or not src.needs_grad:
                 continue
             if src is x and desc.gather1 == RCF_GATHER_NEAREST:
-                dd = ops.make_dgrad_desc(desc, off, cnt, False)
                 tmp = self._new((desc.n, desc.h_in, desc.w_in, cnt), dz)
-                self._run_dgrad(dd, weight, dz, tmp, dz_amax)
-                acc = src.g is not None
-                if acc:
-                    src.bsum = None
-                if not acc:
-                    src.g = self._new(tuple(self._shape(src)), dz)
+                self._fwd_launch(self._exact_unless(ops.make_dgrad_desc(desc, off, cnt, False), dz_amax), weight.detach(), dz, tmp,
+                                 amax_in=dz_amax)
+                acc = self._grad_target(src)
                 ops.upsample_nearest_bwd(tmp, src.g, acc)
-            elif self.use_phase_convs and desc.stride == 2 and desc.ksize == 3 and x2 is None and desc.c1 % 4 == 0:
-                # transposed convolution in 4 phases (16 of the 36 zero-dilated taps are real)
-                acc = src.g is not None
-                if acc:
-                    src.bsum = None
-                if not acc:
-                    src.g = self._new(tuple(self._shape(src)), dz)
+            elif desc.stride == 2 and desc.ksize == 3 and x2 is None and desc.c1 % 4 == 0:
+                # transposed convolution in 4 phases (16 of the 36 zero-dilated taps are real).  In ONE launch over the four output
+                # phases where the library has it (rcf_conv_desc.phase_sum == 3: dz staged once per channel chunk, only the 1 + 2 + 2 + 4
+                # taps that exist -- the four per-phase launches multiply the other seven by zero weights); RCF_S2_DGRAD_ONE_LAUNCH=0
+                # switches it off
+                acc = self._grad_target(src)
                 wd = self._phase_w(weight.detach(), RCF_PHASE_S2_DGRAD)
-                wmax = None
-                if self._s2_dgrad_merged(desc, wd, dz, src.g, acc, dz_amax):
+                dm = self._exact_unless(ops.make_s2_dgrad_desc(desc, 0, 0, acc, phase_out=True), dz_amax)
+                qm = self._one_launch('s2_dgrad', self.s2_dgrad_one_launch, dm)
+                if qm is not None:
+                    self._fwd_launch(dm, wd, dz, src.g, info=qm, amax_in=dz_amax)
                     continue
                 for ph in range(4):
                     d = self._exact_unless(ops.make_s2_dgrad_desc(desc, ph >> 1, ph & 1, acc), dz_amax)
-                    if ph == 0 and self._two_plane(ops.conv_query(d).kernel_id):
-                        wmax = self._w_amax(wd)
-                    self._run_packed(d, wd[ph], dz, src.g, amax_in=dz_amax, amax_w=wmax)
+                    self._fwd_launch(d, wd, dz, src.g, phase=ph, amax_in=dz_amax)
             else:
-                acc = src.g is not None
-                if acc:
-                    src.bsum = None
-                if desc.ksize == 1 and desc.stride == 2 and x2 is None and self._pw_s2_dgrad(desc, weight, dz, src, acc, dz_amax):
-                    continue
-                if not acc:
-                    src.g = self._new(tuple(self._shape(src)), dz)
-                dd = ops.make_dgrad_desc(desc, off, cnt, acc)
-                self._run_dgrad(dd, weight, dz, src.g, dz_amax, sums_for=None if acc else src)
-
-    def _pw_s2_dgrad(self, desc, weight, dz, src, acc, dz_amax):
-        '''The input gradient of a 1x1 stride-2 convolution at dZ's resolution (ops.make_pw_s2_dgrad_desc): W^T dZ written to the even
-        positions of a zero-filled (or accumulated-into) dX -- a quarter of the dense form's pixels, bitwise its result.  Returns False
-        where no kernel takes the strided-output form (remembered per shape); RCF_PW_S2_DGRAD=0 switches it off.'''
-        if not self.pw_s2_dgrad_lowres or ops.act_dtype() != torch.float32:
-            # (bf16 tensors: conv1x1_b16_kernel already skips the zeros of the dilated dZ; the strided-output form measured 0.3 % slower)
-            return False
-        dd = self._exact_unless(ops.make_pw_s2_dgrad_desc(desc, acc), dz_amax)
-        key = bytes(dd)
-        if self._pw_s2_ok.get(key) is False:
-            return False
-        try:
-            info = ops.conv_query(dd)
-        except ops._lib.RcfUnsupported:
-            self._pw_s2_ok[key] = False
-            return False
-        self._pw_s2_ok[key] = True
-        if not acc:
-            src.g = torch.zeros(tuple(self._shape(src)), dtype=ops.act_dtype(), device=dz.device)   # the odd positions stay zero
-        scales = None
-        if self._two_plane(info.kernel_id):
-            wmax = self._w_amax(weight.detach())
-            packed = self._pack(dd, weight.detach(), dz, wmax)
-            scales = ops.make_scales(dz_amax, None, wmax)
-        else:
-            packed = self._pack(dd, weight.detach(), dz)
-        if self.prof is not None:
-            self.prof.begin(info.kernel_id, ops.algorithmic_flops(dd), dd)
-        ops.conv_fwd(dd, dz, None, packed, src.g, None, scales=scales)
-        if self.prof is not None:
-            self.prof.end()
-        return True
+                # a 1x1 stride-2 convolution's input gradient at dZ's resolution (ops.make_pw_s2_dgrad_desc): W^T dZ written to the even
+                # positions of a zero-filled (or accumulated-into) dX -- a quarter of the dense form's pixels, bitwise its result --
+                # where a kernel takes the strided-output form.  RCF_PW_S2_DGRAD=0 switches it off; bf16 tensors keep the dense form
+                # (conv1x1_b16_kernel already skips the zeros of the dilated dZ; the strided-output form measured 0.3 % slower)
+                pw_on = (desc.ksize == 1 and desc.stride == 2 and x2 is None and self.pw_s2_dgrad_lowres
+                         and ops.act_dtype() == torch.float32)
+                dd = self._exact_unless(ops.make_pw_s2_dgrad_desc(desc, src.g is not None), dz_amax) if pw_on else None
+                qm = self._one_launch('pw_s2_dgrad', pw_on, dd)
+                acc = self._grad_target(src, zero=qm is not None)   # (the strided-output form never writes the odd positions)
+                if qm is not None:
+                    # sums_for=None: the library has no BatchNorm-sums epilogue for a strided output (bn_bwd_sums is 0; ADVICE.md, round 6)
+                    self._fwd_launch(dd, weight.detach(), dz, src.g, info=qm, amax_in=dz_amax, sums_for=None)
+                else:
+                    self._fwd_launch(self._exact_unless(ops.make_dgrad_desc(desc, off, cnt, acc), dz_amax), weight.detach(), dz, src.g,
+                                     amax_in=dz_amax, sums_for=None if acc else src)
 
     def _bn_sums_launch(self, dd, info, dz, packed, out, scales, sums_for):
         '''The input-gradient launch `dd` writes sums_for.g for the first time.  If sums_for is the output of a BatchNorm + lrelu block
@@ -1190,29 +973,12 @@ class Engine(object):
         self.bn_sums_taken += 1
         return True
 
-    def _run_dgrad(self, dd, weight, dz, out, dz_amax=None, sums_for=None):
-        dd = self._exact_unless(dd, dz_amax)
-        info = ops.conv_query(dd)
-        scales = None
-        if self._two_plane(info.kernel_id):
-            wmax = self._w_amax(weight.detach())
-            packed = self._pack(dd, weight.detach(), dz, wmax)
-            scales = ops.make_scales(dz_amax, None, wmax)
-        else:
-            packed = self._pack(dd, weight.detach(), dz)
-        if self.prof is not None:
-            self.prof.begin(info.kernel_id, ops.algorithmic_flops(dd), dd)
-        if not self._bn_sums_launch(dd, info, dz, packed, out, scales, sums_for):
-            ops.conv_fwd(dd, dz, None, packed, out, None, scales=scales)
-        if self.prof is not None:
-            self.prof.end()
-
-    def _bn_coef(self, layer, partials, info, z):
+    def _bn_coef(self, layer, partials, rec, z):
         bn = layer.batch_norm
         c = z.shape[3]
         coef = self._newf((4, c), z)
         count = z.shape[0] * z.shape[1] * z.shape[2]
-        ops.bn_finalize(partials, info.n_partials if partials is not None else 0, c, count, bn.weight.detach(),
+        ops.bn_finalize(partials, rec.n_partials if partials is not None else 0, c, count, bn.weight.detach(),
                         bn.bias.detach(), bn.running_mean, bn.running_var, BN_MOMENTUM, BN_EPS, self.training, coef)
         return coef
 
@@ -1242,15 +1008,14 @@ class Engine(object):
             # pipe (rcf_head_fwd_b16) -- BatchNorm-on-load in the head is the TRAINING arrangement (the statistics are not known earlier)
             src = x.t if x.t is not None else (x.z if x.z is not None else x.s2d)
             coef = self._bn_coef_eval(layer, src)
-            z, desc, info, partials, fused = self._conv(layer, x, x2, up_hw, want_stats=False,
-                                                        fold=(coef, None if res is None else self._mat(res)))
-            if fused:
+            z, rec, partials = self._conv(layer, x, x2, up_hw, want_stats=False, fold=(coef, None if res is None else self._mat(res)))
+            if rec.fused:
                 out = Act(z)
                 out.head_fusable = False
                 return out
         else:
-            z, desc, info, partials = self._conv(layer, x, x2, up_hw, want_stats=self.training)
-            coef = self._bn_coef(layer, partials, info, z)
+            z, rec, partials = self._conv(layer, x, x2, up_hw, want_stats=self.training)
+            coef = self._bn_coef(layer, partials, rec, z)
         n_pix = z.shape[0] * z.shape[1] * z.shape[2]
         c = z.shape[3]
         if res is None and (self.bn_on_load or (feeds_head and ops.head_bn_blocks(z.shape[0], z.shape[1], z.shape[2], c) > 0)):
@@ -1288,7 +1053,7 @@ class Engine(object):
                     dz = torch.empty_like(z)
                     dz_amax = self._amax_slot() if z.dtype == torch.float32 else None
                     ops.head_bn_bwd_apply(dlogit, w_head, z, coef, bcoef, dz, amax=dz_amax)
-                    self._conv_backward(layer, desc, info, x, x2, dz, dz_amax)
+                    self._conv_backward(layer, rec, x, x2, dz, dz_amax)
                     return
                 dout = out.g
                 has_res = res is not None   # out.t is read only then (a deferred activation has no residual)
@@ -1307,16 +1072,12 @@ class Engine(object):
                 dz = torch.empty_like(z)
                 dres, dres_acc = None, False
                 if has_res and res.needs_grad:
-                    dres_acc = res.g is not None
-                    if dres_acc:
-                        res.bsum = None
-                    if not dres_acc:
-                        res.g = torch.empty_like(res.t)
+                    dres_acc = self._grad_target(res)
                     dres = res.g
                 dz_amax = self._amax_slot() if z.dtype == torch.float32 else None
                 ops.bn_act_bwd_apply(dout, z, coef, out.t, bcoef, dz, dres, dres_acc, n_pix, c, RCF_ACT_LEAKY_RELU, has_res, amax=dz_amax)
                 out.g = None
-                self._conv_backward(layer, desc, info, x, x2, dz, dz_amax)
+                self._conv_backward(layer, rec, x, x2, dz, dz_amax)
 
             self.tape.append(backward)
         return out
@@ -1325,7 +1086,7 @@ class Engine(object):
         '''Conv2d without BN and activation (ResNetBlock.projection, src/net_utils.py:300-307).'''
         if layer.use_batch_norm or layer.activation_func is not None:
             raise ValueError('conv_plain expects a bare conv')
-        z, desc, info, _ = self._conv(layer, x)
+        z, rec, _ = self._conv(layer, x)
         out = Act(z)
         if self.tape is not None:
             scope = self._scope
@@ -1334,7 +1095,7 @@ class Engine(object):
                 self._set_scope(scope)
                 dz = out.g
                 out.g = None
-                self._conv_backward(layer, desc, info, x, None, dz)
+                self._conv_backward(layer, rec, x, None, dz)
             self.tape.append(backward)
         return out
 
@@ -1351,10 +1112,10 @@ class Engine(object):
                 ops.fuse_wp_infer(dt, layer_w.conv.weight.detach(), self._bn_coef_eval(layer_w, it), layer_p.conv.weight.detach(),
                                   self._bn_coef_eval(layer_p, it), it, out.t)
                 return out
-        zw, dw_, iw, pw = self._conv(layer_w, dep, want_stats=self.training)
-        zp, dp_, ip, pp = self._conv(layer_p, dep, want_stats=self.training)
-        coef_w = self._bn_coef(layer_w, pw, iw, zw)
-        coef_p = self._bn_coef(layer_p, pp, ip, zp)
+        zw, rec_w, pw = self._conv(layer_w, dep, want_stats=self.training)
+        zp, rec_p, pp = self._conv(layer_p, dep, want_stats=self.training)
+        coef_w = self._bn_coef(layer_w, pw, rec_w, zw)
+        coef_p = self._bn_coef(layer_p, pp, rec_p, zp)
         n_pix = zw.shape[0] * zw.shape[1] * zw.shape[2]
         c = zw.shape[3]
         out = Act(torch.empty_like(zw))
@@ -1384,11 +1145,7 @@ class Engine(object):
                 dzp = torch.empty_like(zp)
                 dimg, dimg_acc = None, False
                 if img.needs_grad:
-                    dimg_acc = img.g is not None
-                    if dimg_acc:
-                        img.bsum = None
-                    if not dimg_acc:
-                        img.g = torch.empty_like(img.t)
+                    dimg_acc = self._grad_target(img)
                     dimg = img.g
                 ops.fuse_bwd_apply(dout, zw, coef_w, zp, coef_p, bcw, bcp, dzw, dzp, dimg, dimg_acc, n_pix, c)
                 out.g = None
@@ -1396,8 +1153,8 @@ class Engine(object):
                 br = self._branch_enter(first_wait=True)
                 if br is not None:
                     self._side_keep.extend((dzw, dzp, zw, zp))
-                self._conv_backward(layer_w, dw_, iw, dep, None, dzw)
-                self._conv_backward(layer_p, dp_, ip, dep, None, dzp)
+                self._conv_backward(layer_w, rec_w, dep, None, dzw)
+                self._conv_backward(layer_p, rec_p, dep, None, dzp)
                 self._branch_exit(br)
 
             self.tape.append(backward)
@@ -1414,11 +1171,7 @@ class Engine(object):
         ops.maxpool_fwd(xt, out.t, idx)
         if self.tape is not None:
             def backward():
-                acc = x.g is not None
-                if acc:
-                    x.bsum = None
-                if not acc:
-                    x.g = torch.empty_like(x.t)
+                acc = self._grad_target(x)
                 ops.maxpool_bwd(out.g, idx, x.g, acc)
                 out.g = None
             self.tape.append(backward)
@@ -1583,18 +1336,13 @@ class Engine(object):
                 if x.needs_grad and out.g is not None:
                     # gathered per input pixel (rcf_roi_pool_bwd_gather): written once in the tensors' own storage -- the scatter form
                     # (rcf_roi_pool_bwd: fp32 atomics into a zeroed copy) stays in the ABI
-                    acc = x.g is not None
-                    if acc:
-                        x.bsum = None
                     if rois.shape[0] <= 1024:
-                        if not acc:
-                            x.g = torch.empty_like(xt)
+                        acc = self._grad_target(x)
                         ops.roi_pool_bwd_gather(out.g, argmax, rois, x.g, acc, out_hw, scale, dout_coff=coff)
                     else:   # more rois than the gather form's table holds: scatter-add into a zeroed fp32 tensor, then join the gradient
                         tmp = torch.zeros(xt.shape, dtype=torch.float32, device=xt.device)
                         ops.roi_pool_bwd(out.g, argmax, rois, tmp, out_hw, dout_coff=coff)
-                        if not acc:
-                            x.g = torch.empty_like(xt)
+                        acc = self._grad_target(x)
                         ops.convert(tmp, x.g, accumulate=acc)
             self.tape.append(backward)
         return out

@@ -62,9 +62,9 @@ up_calls = []
 orig_up = eng_mod.Engine._conv_up2x_backward
 
 
-def up_wrapped(self, layer, info, x, dz, dz_amax=None):
+def up_wrapped(self, layer, rec, x, dz, dz_amax=None):
     had = x.g is not None
-    orig_up(self, layer, info, x, dz, dz_amax)
+    orig_up(self, layer, rec, x, dz, dz_amax)
     torch.cuda.synchronize()
     if had or x.g is None:
         return

@@ -88,11 +88,11 @@ def cba(layer, x, x2=None, up_hw=None, res=None, feeds_head=False):
 E.conv_bn_act = cba
 zrec = {}
 orig_cb = E._conv_backward
-def cb(layer, desc, info, x, x2, dz, dz_amax=None):
+def cb(layer, rec_, x, x2, dz, dz_amax=None):
     nm = names.get(id(layer))
     if nm is not None:
         zrec.setdefault(nm, {})['dz'] = dz.clone()
-    return orig_cb(layer, desc, info, x, x2, dz, dz_amax)
+    return orig_cb(layer, rec_, x, x2, dz, dz_amax)
 E._conv_backward = cb
 orig_conv = E._conv
 def cv(layer, x, x2=None, up_hw=None, want_stats=False, fold=None):
