@@ -764,49 +764,6 @@ __global__ void __launch_bounds__(256, 2) conv_b16_kernel(ConvArgs a) {
     }
 }
 
-template <class C>
-int dma_grid_x(int ntiles, int ntile_n) {
-    static int resident = 0;
-    if (resident == 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_b16_kernel<C, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  C::LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_b16_kernel<C, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  C::LDS_BYTES);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_b16_kernel<C, false>, 256, C::LDS_BYTES) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        resident = per_cu * num_cus();
-    }
-    int gx = resident / ntile_n;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
-    return gx;
-}
-
-template <class C, bool EPI = false>
-int launch_dma(const ConvArgs& a_, int ntile_n, hipStream_t st) {
-    ConvArgs a = a_;
-#ifdef RCF_B16_DIAG
-    { const char* dg = getenv("RCF_B16_DIAG"); if (dg && dg[0] == '1') a.xcd_band += 64; }
-#endif
-    const int gx = dma_grid_x<C>(a.ntiles, ntile_n);
-    hipLaunchKernelGGL((conv_b16_kernel<C, EPI>), dim3(gx, ntile_n, 1), dim3(256), C::LDS_BYTES, st, a);
-    return rcf_launch_status();
-}
-
-template <class C>
-int launch_dma_bst(const ConvArgs& a, int ntile_n, hipStream_t st) {
-    const int gx = dma_grid_x<C>(a.ntiles, ntile_n);
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_b16_kernel<C, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  C::LDS_BYTES);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv_b16_kernel<C, false, true>), dim3(gx, ntile_n, 1), dim3(256), C::LDS_BYTES, st, a);
-    return rcf_launch_status();
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 // conv1x1_b16_kernel: 1x1 convolutions (the encoder's fusion convs W1 d, W2 d and the ResNet projections, src/networks.py:863-866,
 // src/net_utils.py:300-307) and their input gradients on bf16 tensors.  A 1x1 convolution is a [pixels x Cin] x [Cin x Cout] GEMM with
@@ -1003,25 +960,4 @@ inline int pw_grid(long long npix, int kst, int nt, int gy) {
     if (g > trips) g = trips;
     if (g < 1) g = 1;
     return (int)g;
-}
-
-template <class C>
-int launch_pw(const ConvArgs& a, hipStream_t st) {
-    static_assert(C::MT == (C::KST >= 8 ? 1 : (C::NT <= 2 ? 4 : 1)), "pw_mt mirrors PwCfg::MT");
-    const int gy = (a.c_out + 32 * C::NT - 1) / (32 * C::NT);
-    const int g = pw_grid((long long)a.n * a.h_out * a.w_out, C::KST, C::NT, gy);
-    hipLaunchKernelGGL((conv1x1_b16_kernel<C>), dim3(g, gy), dim3(256), 0, st, a);
-    return rcf_launch_status();
-}
-
-template <class F>
-int dispatch_pw(int kst, int nt, F&& f) {
-#define RCF_PW(K, N) if (kst == K && nt == N) return f(PwCfg<K, N>{})
-    RCF_PW(1, 1); RCF_PW(1, 2); RCF_PW(1, 3); RCF_PW(1, 4);
-    RCF_PW(2, 1); RCF_PW(2, 2); RCF_PW(2, 3); RCF_PW(2, 4);
-    RCF_PW(3, 1); RCF_PW(3, 2);
-    RCF_PW(4, 1); RCF_PW(4, 2); RCF_PW(4, 3);
-    RCF_PW(8, 1); RCF_PW(8, 2); RCF_PW(16, 1);
-#undef RCF_PW
-    return RCF_EUNSUPPORTED;
 }

@@ -2486,7 +2486,7 @@ __global__ void phase_wgrad_gather_s2_kernel(const float* __restrict__ dwp, floa
 }   // namespace
 #else
 // ------------------------------------------------------------------------------------------------
-// configuration tables
+// selection
 enum Kind { K3S1 = 0, K3S2 = 1, K1 = 2, K7S2 = 3, K2S1 = 4, K4S1 = 7 };   // K4S1: the 7x7 stride-2 stem as a 4x4 conv on the space-to-depth image (bf16 tensors; fp32 tensors on two fp16 planes)
 
 struct Sel {
@@ -2517,242 +2517,48 @@ int num_cus() {
 }   // namespace
 namespace {
 #include "rcf_conv_b16_dma.h"
-using D3_2_32 = DmaCfg<3, 2, 32, 2>;
-using D3_2_16 = DmaCfg<3, 2, 16, 2>;
-using D3_1_32 = DmaCfg<3, 1, 32, 4>;     // 32-co layers: 512-pixel tiles
-using D3_1_16 = DmaCfg<3, 1, 16, 4>;
-using D3_1_32s = DmaCfg<3, 1, 32, 2>;    // small layers: 256-pixel x 32-co workgroups
-using D3_1_16s = DmaCfg<3, 1, 16, 2>;
-using D2_2_32 = DmaCfg<2, 2, 32, 2>;
-using D2_2_16 = DmaCfg<2, 2, 16, 2>;
-using D2_1_32 = DmaCfg<2, 1, 32, 2>;
-using D2_1_16 = DmaCfg<2, 1, 16, 2>;
-// up-2x forward, four phases from one tile: 256 pixels x 32 co x 4 phases per workgroup, or 128 pixels x 64 co (the four accumulator
-// sets are 128 registers either way).  32-pixel tile rows only: the 16-pixel form (per-read LDS addresses) spills
-using D2P4_1_32 = DmaCfg<2, 1, 32, 2, 1, 1>;
-using D2P4_2_32 = DmaCfg<2, 2, 32, 1, 1, 1>;
-using D2S2_1_32 = DmaCfg<2, 1, 32, 2, 1, 2>;   // stride-2 input gradient, four output phases from one dz tile
-using D2S2_2_32 = DmaCfg<2, 2, 32, 1, 1, 2>;
-using D3S2_2_32 = DmaCfg<3, 2, 32, 1, 2>;   // stride 2: 128-pixel tiles (the 65 x 9 halo tile is 18 KB per buffer)
-using D3S2_2_16 = DmaCfg<3, 2, 16, 1, 2>;
-using D3S2_1_32 = DmaCfg<3, 1, 32, 1, 2>;
-using D3S2_1_16 = DmaCfg<3, 1, 16, 1, 2>;
-using D4_1_32 = DmaCfg<4, 1, 32, 2>;        // the stems: 4x4 on the 16-channel space-to-depth image, <= 32 output channels
-using D4_1_16 = DmaCfg<4, 1, 16, 2>;
 #else
 }   // namespace
 namespace {
 #include "rcf_conv_pw_f16x2.h"
 #endif
 
-// Persistent grid: one resident wave of workgroups (occupancy API), split between the n-tiles.  Also the number of
-// BN-statistics partial rows the kernel writes, so rcf_conv2d_query reports the same number.
-template <class C>
-int fwd_grid_x(int ntiles, int ntile_n) {
-    static int resident = 0;   // workgroups that fit on the device at once
-    if (resident == 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_fwd_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  C::LDS_BYTES);
+// ------------------------------------------------------------------------------------------------
+// launching
+
+// the dynamic-LDS limit of kernel K, raised on its first use
+template <auto K>
+void lds_attr(int lds) {
+    static const bool done =
+        lds > 0 && hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+    (void)done;
+}
+
+template <auto K>
+int launch(dim3 grid, dim3 block, int lds, hipStream_t st, const ConvArgs& a) {
+    lds_attr<K>(lds);
+    hipLaunchKernelGGL(K, grid, block, lds, st, a);
+    return rcf_launch_status();
+}
+
+// Persistent grid: one resident wave of workgroups (occupancy API), split between the n-tiles.  K is always the plain instantiation
+// of a configuration (no inference epilogue, no BatchNorm sums): its gx is also the grid of those variants and the number of
+// BN-statistics partial rows the kernel writes, which rcf_conv2d_query reports.
+template <auto K>
+int resident_grid_x(int lds, int ntiles, int ntile_n) {
+    static const int resident = [lds] {   // workgroups that fit on the device at once
+        lds_attr<K>(lds);
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_fwd_kernel<C>, 256, C::LDS_BYTES) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        resident = per_cu * num_cus();
-    }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K, 256, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+        return per_cu * num_cus();
+    }();
     int gx = resident / ntile_n;
     if (gx < 1) gx = 1;
     if (gx > ntiles) gx = ntiles;
     return gx;
 }
-
-template <class C>
-int launch_fwd(const ConvArgs& a, int ntile_n, hipStream_t st) {
-    const int gx = fwd_grid_x<C>(a.ntiles, ntile_n);
-    dim3 grid(gx, ntile_n, 1);
-    hipLaunchKernelGGL((conv_fwd_kernel<C>), grid, dim3(256), C::LDS_BYTES, st, a);
-    return rcf_launch_status();
-}
-
-template <class C>
-int split_grid_x(int ntiles, int ntile_n) {
-    static int resident = 0;
-    if (resident == 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_split_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  C::LDS_BYTES);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_split_kernel<C>, 256, C::LDS_BYTES) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        resident = per_cu * num_cus();
-    }
-    int gx = resident / ntile_n;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
-    return gx;
-}
-
-template <class C, bool EPI = false>
-int launch_split(const ConvArgs& a, int ntile_n, hipStream_t st) {
-    const int gx = split_grid_x<C>(a.ntiles, ntile_n);
-    if (EPI) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_split_kernel<C, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      C::LDS_BYTES);
-            attr_done = true;
-        }
-    }
-    hipLaunchKernelGGL((conv_split_kernel<C, EPI>), dim3(gx, ntile_n, 1), dim3(256), C::LDS_BYTES, st, a);
-    return rcf_launch_status();
-}
-
-// the input-gradient launch that also takes the BatchNorm-backward sums of the block whose dY it writes (ConvArgs.bz / bk)
-template <class C>
-int launch_split_bst(const ConvArgs& a, int ntile_n, hipStream_t st) {
-    const int gx = split_grid_x<C>(a.ntiles, ntile_n);
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_split_kernel<C, false, SAct, SAct, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv_split_kernel<C, false, SAct, SAct, true>), dim3(gx, ntile_n, 1), dim3(256), C::LDS_BYTES, st, a);
-    return rcf_launch_status();
-}
-
-
-template <class C>
-int launch_wgrad(const ConvArgs& a, int nsplit, int nchunk, int ncog, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  C::LDS_BYTES);
-        attr_done = true;
-    }
-    dim3 grid(nsplit, nchunk, ncog);
-    hipLaunchKernelGGL((conv_wgrad_kernel<C>), grid, dim3(256), C::LDS_BYTES, st, a);
-    return rcf_launch_status();
-}
-
-template <class C>
-int launch_wgrad_split(const ConvArgs& a, int nsplit, int gy, int gz, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_split_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  C::LDS_BYTES);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv_wgrad_split_kernel<C>), dim3(nsplit, gy, gz), dim3(256), C::LDS_BYTES, st, a);
-    return rcf_launch_status();
-}
-
-template <class C>
-int launch_wgrad_tr(const ConvArgs& a, int nsplit, int gy, int gz, hipStream_t st) {
-    constexpr int lds = C::template lds_bytes<SAct::B16>();
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tr_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv_wgrad_tr_kernel<C>), dim3(nsplit, gy, gz), dim3(512), lds, st, a);
-    return rcf_launch_status();
-}
-
-#if RCF_CONV_B16
-#define RCF_DMA(expr) RCF_EUNSUPPORTED   /* LDS-DMA copies fp32 tiles verbatim: fp32 tensors only */
-#else
-#define RCF_DMA(expr) (expr)
-#endif
-template <class C>
-int launch_wgrad_dma(const ConvArgs& a, int nsplit, int nchunk, int ncog, hipStream_t st) {
-    using H = Halo<C::CST, C::STRP, C::HXP, C::HYP>;
-    constexpr int red_floats = C::T * 16 * 64;
-    constexpr int tile_floats = H::NA * H::PPI * 32 + C::TP * 32;
-    constexpr int lds_bytes = (tile_floats > red_floats ? tile_floats : red_floats) * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  lds_bytes);
-        attr_done = true;
-    }
-    dim3 grid(nsplit, nchunk, ncog);
-    hipLaunchKernelGGL((conv_wgrad_dma_kernel<C>), grid, dim3(256), lds_bytes, st, a);
-    return rcf_launch_status();
-}
-
-//                 KSY KSX XE LS  CK CST STRP NT PX MINW
-using F3S1_16_1_32 = FwdCfg<3, 3, 0, 1, 16, 16, 20, 1, 32, 2>;
-using F3S1_16_2_32 = FwdCfg<3, 3, 0, 1, 16, 16, 20, 2, 32, 2>;
-using F3S1_16_1_16 = FwdCfg<3, 3, 0, 1, 16, 16, 20, 1, 16, 2>;
-using F3S1_16_2_16 = FwdCfg<3, 3, 0, 1, 16, 16, 20, 2, 16, 2>;
-using F3S1_16_1_8 = FwdCfg<3, 3, 0, 1, 16, 16, 20, 1, 8, 2>;
-using F3S1_16_2_8 = FwdCfg<3, 3, 0, 1, 16, 16, 20, 2, 8, 2>;
-using F3S1_8_1_32 = FwdCfg<3, 3, 0, 1, 8, 8, 12, 1, 32, 2>;
-using F3S1_8_2_32 = FwdCfg<3, 3, 0, 1, 8, 8, 12, 2, 32, 2>;
-using F3S1_8_1_16 = FwdCfg<3, 3, 0, 1, 8, 8, 12, 1, 16, 2>;
-using F3S1_8_2_16 = FwdCfg<3, 3, 0, 1, 8, 8, 12, 2, 16, 2>;
-using F3S2_8_1_32 = FwdCfg<3, 3, 0, 2, 8, 8, 12, 1, 32, 1>;
-using F3S2_8_2_32 = FwdCfg<3, 3, 0, 2, 8, 8, 12, 2, 32, 1>;
-using F3S2_8_1_16 = FwdCfg<3, 3, 0, 2, 8, 8, 12, 1, 16, 1>;
-using F3S2_8_2_16 = FwdCfg<3, 3, 0, 2, 8, 8, 12, 2, 16, 1>;
-using F1_32_1_32 = FwdCfg<1, 1, 0, 1, 32, 32, 36, 1, 32, 2>;
-using F1_32_2_32 = FwdCfg<1, 1, 0, 1, 32, 32, 36, 2, 32, 2>;
-using F1_32_1_16 = FwdCfg<1, 1, 0, 1, 32, 32, 36, 1, 16, 2>;
-using F1_32_2_16 = FwdCfg<1, 1, 0, 1, 32, 32, 36, 2, 16, 2>;
-using F1_16_1_32 = FwdCfg<1, 1, 0, 1, 16, 16, 20, 1, 32, 2>;
-using F1_16_2_32 = FwdCfg<1, 1, 0, 1, 16, 16, 20, 2, 32, 2>;
-using F1_16_1_16 = FwdCfg<1, 1, 0, 1, 16, 16, 20, 1, 16, 2>;
-using F1_16_2_16 = FwdCfg<1, 1, 0, 1, 16, 16, 20, 2, 16, 2>;
-using F2_32_1_32 = FwdCfg<2, 2, 0, 1, 32, 32, 36, 1, 32, 2>;
-using F2_32_2_32 = FwdCfg<2, 2, 0, 1, 32, 32, 36, 2, 32, 2>;
-using F2_32_1_16 = FwdCfg<2, 2, 0, 1, 32, 32, 36, 1, 16, 2>;
-using F2_32_2_16 = FwdCfg<2, 2, 0, 1, 32, 32, 36, 2, 16, 2>;
-using F7_32 = FwdCfg<7, 1, 7, 2, 32, 4, 4, 1, 32, 2>;
-using S3_1_32 = SplitCfg<3, 1, 32>;
-using S3_2_32 = SplitCfg<3, 2, 32>;
-using S3_1_16 = SplitCfg<3, 1, 16>;
-using S3_2_16 = SplitCfg<3, 2, 16>;
-using B3_1_32 = SplitCfg<3, 1, 32, 0, 1>;    // bf16-operand variants (one plane, one product)
-using B3_2_32 = SplitCfg<3, 2, 32, 0, 1>;
-using B3_1_16 = SplitCfg<3, 1, 16, 0, 1>;
-using B3_2_16 = SplitCfg<3, 2, 16, 0, 1>;
-using B2_1_32 = SplitCfg<2, 1, 32, 0, 1>;
-using B2_2_32 = SplitCfg<2, 2, 32, 0, 1>;
-using B2_1_16 = SplitCfg<2, 1, 16, 0, 1>;
-using B2_2_16 = SplitCfg<2, 2, 16, 0, 1>;
-using B3_1_32s = SplitCfg<3, 1, 32, 2, 1>;
-using B3_1_16s = SplitCfg<3, 1, 16, 2, 1>;
-using S3_1_32s = SplitCfg<3, 1, 32, 2>;   // 256-pixel x 32-co workgroups: more of them for the small layers
-using S3_1_16s = SplitCfg<3, 1, 16, 2>;
-using S3S2_1_32 = SplitCfg<3, 1, 32, 1, 3, 2>;   // 3x3 stride 2, three planes: 128-pixel tiles (the 65 x 9 halo tile in three planes is 56 KB)
-using S3S2_2_32 = SplitCfg<3, 2, 32, 1, 3, 2>;
-using S3S2_1_16 = SplitCfg<3, 1, 16, 1, 3, 2>;
-using S3S2_2_16 = SplitCfg<3, 2, 16, 1, 3, 2>;
-using B3S2_1_32 = SplitCfg<3, 1, 32, 2, 1, 2>;   // bf16 operands: one plane, 256-pixel tiles, two workgroups per CU
-using B3S2_2_32 = SplitCfg<3, 2, 32, 2, 1, 2>;
-using B3S2_1_16 = SplitCfg<3, 1, 16, 2, 1, 2>;
-using B3S2_2_16 = SplitCfg<3, 2, 16, 2, 1, 2>;
-using S2_1_32 = SplitCfg<2, 1, 32>;
-using S2_2_32 = SplitCfg<2, 2, 32>;
-using S2_1_16 = SplitCfg<2, 1, 16>;
-using S2_2_16 = SplitCfg<2, 2, 16>;
-using F7_16 = FwdCfg<7, 1, 7, 2, 32, 4, 4, 1, 16, 2>;
-
-//               KSY KSX XE LS CST STRP PX TH MINW
-using W3S1_32 = WgCfg<3, 3, 0, 1, 32, 32, 32, 8, 1>;
-using W3S1_16 = WgCfg<3, 3, 0, 1, 32, 32, 16, 16, 1>;
-using W3S1_8 = WgCfg<3, 3, 0, 1, 32, 32, 8, 32, 1>;
-using W3S2_32 = WgCfg<3, 3, 0, 2, 32, 32, 32, 4, 1>;
-using W3S2_16 = WgCfg<3, 3, 0, 2, 32, 32, 16, 8, 1>;
-using W1_32 = WgCfg<1, 1, 0, 1, 32, 32, 32, 8, 2>;
-using W1_16 = WgCfg<1, 1, 0, 1, 32, 32, 16, 16, 2>;
-using W2_32 = WgCfg<2, 2, 0, 1, 32, 32, 32, 8, 1>;
-using W2_16 = WgCfg<2, 2, 0, 1, 32, 32, 16, 16, 1>;
-using W7_32 = WgCfg<7, 1, 7, 2, 4, 4, 32, 8, 2>;
-using W7_16 = WgCfg<7, 1, 7, 2, 4, 4, 16, 16, 2>;
 
 int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-template <class T>
-struct Tag { using type = T; };
 
 // tile utilisation of a PX x TH tiling of a w x h image
 double tile_eff(int w, int h, int px, int th) {
@@ -2975,10 +2781,10 @@ const float* zero_page_ptr() {
     return p;
 }
 
-void fill_args(const rcf_conv_desc* d, const Sel& s, ConvArgs* a) {
-    a->coef1 = nullptr; a->coef2 = nullptr; a->bias = nullptr; a->res = nullptr;
-    a->amax_a1 = nullptr; a->amax_a2 = nullptr; a->amax_b = nullptr;
-    a->bz = nullptr; a->bk = nullptr;
+// the launch arguments a tiling S (Sel or WSel: px, th, vt, cst) fixes; the callers add their tensors
+template <class S>
+void fill_args(const rcf_conv_desc* d, const S& s, ConvArgs* a) {
+    *a = ConvArgs{};
     a->zero = zero_page_ptr();
     a->n = d->n; a->h_in = d->h_in; a->w_in = d->w_in; a->c1 = d->c1; a->c2 = d->c2;
     a->h1 = d->h_src1; a->w1 = d->w_src1; a->gather1 = d->gather1;
@@ -2987,7 +2793,7 @@ void fill_args(const rcf_conv_desc* d, const Sel& s, ConvArgs* a) {
     a->accumulate = d->accumulate;
     a->os = d->out_stride; a->ooy = d->out_off_y; a->oox = d->out_off_x; a->ohp = d->out_h_phys; a->owp = d->out_w_phys;
     a->ioy = d->in_off_y; a->iox = d->in_off_x;
-    a->phase_sum = d->phase_sum; a->wp_phase_stride = 0;
+    a->phase_sum = d->phase_sum;
     a->sy = (float)d->h_src1 / (float)d->h_in;
     a->sx = (float)d->w_src1 / (float)d->w_in;
     a->tiles_x = ceil_div(d->w_out, s.px);
@@ -3005,134 +2811,6 @@ void fill_args(const rcf_conv_desc* d, const Sel& s, ConvArgs* a) {
     // profiles/r04_xcd_bands.txt); RCF_XCD_BANDS=0 restores the round-robin deal for an A/B
     static const int xcd_band = [] { const char* e = getenv("RCF_XCD_BANDS"); return e ? atoi(e) : 1; }();
     a->xcd_band = xcd_band;
-}
-
-template <class F>
-int dispatch_fwd(const Sel& s, F&& f) {
-    const bool p16 = s.px == 16;
-    switch (s.kind) {
-        case K3S1:
-            if (s.ck == 16) {
-                if (s.px == 8) return s.nt == 1 ? f(Tag<F3S1_16_1_8>{}) : f(Tag<F3S1_16_2_8>{});
-                if (s.nt == 1) return p16 ? f(Tag<F3S1_16_1_16>{}) : f(Tag<F3S1_16_1_32>{});
-                return p16 ? f(Tag<F3S1_16_2_16>{}) : f(Tag<F3S1_16_2_32>{});
-            }
-            if (s.nt == 1) return p16 ? f(Tag<F3S1_8_1_16>{}) : f(Tag<F3S1_8_1_32>{});
-            return p16 ? f(Tag<F3S1_8_2_16>{}) : f(Tag<F3S1_8_2_32>{});
-        case K3S2:
-            if (s.nt == 1) return p16 ? f(Tag<F3S2_8_1_16>{}) : f(Tag<F3S2_8_1_32>{});
-            return p16 ? f(Tag<F3S2_8_2_16>{}) : f(Tag<F3S2_8_2_32>{});
-        case K1:
-            if (s.ck == 32) {
-                if (s.nt == 1) return p16 ? f(Tag<F1_32_1_16>{}) : f(Tag<F1_32_1_32>{});
-                return p16 ? f(Tag<F1_32_2_16>{}) : f(Tag<F1_32_2_32>{});
-            }
-            if (s.nt == 1) return p16 ? f(Tag<F1_16_1_16>{}) : f(Tag<F1_16_1_32>{});
-            return p16 ? f(Tag<F1_16_2_16>{}) : f(Tag<F1_16_2_32>{});
-        case K7S2:
-            return p16 ? f(Tag<F7_16>{}) : f(Tag<F7_32>{});
-        case K2S1:
-            if (s.nt == 1) return p16 ? f(Tag<F2_32_1_16>{}) : f(Tag<F2_32_1_32>{});
-            return p16 ? f(Tag<F2_32_2_16>{}) : f(Tag<F2_32_2_32>{});
-    }
-    return RCF_EUNSUPPORTED;
-}
-
-#if RCF_CONV_B16
-template <class F>
-int dispatch_dma(const Sel& s, F&& f) {
-    const bool p16 = s.px == 16;
-    if (s.kind == K2S1 && s.p4 == 2) return s.nt == 1 ? f(Tag<D2S2_1_32>{}) : f(Tag<D2S2_2_32>{});
-    if (s.kind == K2S1 && s.p4) return s.nt == 1 ? f(Tag<D2P4_1_32>{}) : f(Tag<D2P4_2_32>{});
-    if (s.kind == K2S1) {
-        if (s.nt == 1) return p16 ? f(Tag<D2_1_16>{}) : f(Tag<D2_1_32>{});
-        return p16 ? f(Tag<D2_2_16>{}) : f(Tag<D2_2_32>{});
-    }
-    if (s.kind == K4S1) return p16 ? f(Tag<D4_1_16>{}) : f(Tag<D4_1_32>{});
-    if (s.kind == K3S2) {
-        if (s.nt == 1) return p16 ? f(Tag<D3S2_1_16>{}) : f(Tag<D3S2_1_32>{});
-        return p16 ? f(Tag<D3S2_2_16>{}) : f(Tag<D3S2_2_32>{});
-    }
-    if (s.nt == 1 && s.small) return p16 ? f(Tag<D3_1_16s>{}) : f(Tag<D3_1_32s>{});
-    if (s.nt == 1) return p16 ? f(Tag<D3_1_16>{}) : f(Tag<D3_1_32>{});
-    return p16 ? f(Tag<D3_2_16>{}) : f(Tag<D3_2_32>{});
-}
-#endif
-
-// fp32 tensors: NPL = 3 (the S* configurations above: exact) or NPL = 2 (RCF_PREC_F16X2), same tile shapes
-template <int NPL, class F>
-int dispatch_split_planes(const Sel& s, F&& f) {
-    const bool p16 = s.px == 16;
-    if (s.kind == K4S1) {   // the stems on the fp32 space-to-depth image: 4x4 taps, 16 channels, <= 32 output channels, two planes only
-        if constexpr (NPL == 2) return p16 ? f(Tag<SplitCfg<4, 1, 16, 0, 2>>{}) : f(Tag<SplitCfg<4, 1, 32, 0, 2>>{});
-        else return RCF_EUNSUPPORTED;
-    }
-    if (s.kind == K3S2) {
-        if (s.nt == 1) return p16 ? f(Tag<SplitCfg<3, 1, 16, 1, NPL, 2>>{}) : f(Tag<SplitCfg<3, 1, 32, 1, NPL, 2>>{});
-        return p16 ? f(Tag<SplitCfg<3, 2, 16, 1, NPL, 2>>{}) : f(Tag<SplitCfg<3, 2, 32, 1, NPL, 2>>{});
-    }
-    if (s.kind == K2S1 && s.p4) {   // (select_cfg: two planes, 32-pixel tile rows; 64 co: 128-pixel tiles -- four accumulator sets)
-        if constexpr (NPL == 2) {
-            if (s.p4 == 2) return s.nt == 1 ? f(Tag<SplitCfg<2, 1, 32, 0, 2, 1, 2>>{}) : f(Tag<SplitCfg<2, 2, 32, 1, 2, 1, 2>>{});
-            return s.nt == 1 ? f(Tag<SplitCfg<2, 1, 32, 0, 2, 1, 1>>{}) : f(Tag<SplitCfg<2, 2, 32, 1, 2, 1, 1>>{});
-        } else return RCF_EUNSUPPORTED;
-    }
-    if (s.kind == K2S1) {
-        if (s.nt == 1) return p16 ? f(Tag<SplitCfg<2, 1, 16, 0, NPL>>{}) : f(Tag<SplitCfg<2, 1, 32, 0, NPL>>{});
-        return p16 ? f(Tag<SplitCfg<2, 2, 16, 0, NPL>>{}) : f(Tag<SplitCfg<2, 2, 32, 0, NPL>>{});
-    }
-    if (s.nt == 1 && s.small) return p16 ? f(Tag<SplitCfg<3, 1, 16, 2, NPL>>{}) : f(Tag<SplitCfg<3, 1, 32, 2, NPL>>{});
-    if (s.nt == 1) return p16 ? f(Tag<SplitCfg<3, 1, 16, 0, NPL>>{}) : f(Tag<SplitCfg<3, 1, 32, 0, NPL>>{});
-    return p16 ? f(Tag<SplitCfg<3, 2, 16, 0, NPL>>{}) : f(Tag<SplitCfg<3, 2, 32, 0, NPL>>{});
-}
-
-// configurations that exist with the BatchNorm-backward sums in the epilogue (rcf_conv_info.bn_bwd_sums): fp32 tensors, two fp16
-// planes, 3x3 stride 1 and 2x2 (the four-phase input gradient of an up-2x convolution in one launch)
-bool split_bst_ok(const Sel& s) {
-#if RCF_CONV_B16
-    // conv_b16_kernel<C, false, true>: every 3x3 stride-1 and 2x2 configuration (round 5: the buffer-addressed epilogue freed ~40
-    // registers; the 64-co x 32-pixel-row one had been excluded for its spills)
-    return s.dma && !s.pw && (s.kind == K2S1 || s.kind == K3S1);
-#else
-    return s.split && !s.bf16 && s.npl == 2 && (s.kind == K3S1 || s.kind == K2S1);
-#endif
-}
-template <class F>
-int dispatch_split_bst(const Sel& s, F&& f) {
-    if constexpr (!SAct::B16) {
-        if (!split_bst_ok(s)) return RCF_EUNSUPPORTED;
-        const bool p16 = s.px == 16;
-        if (s.kind == K2S1) {
-            if (s.nt == 1) return p16 ? f(Tag<SplitCfg<2, 1, 16, 0, 2>>{}) : f(Tag<SplitCfg<2, 1, 32, 0, 2>>{});
-            return p16 ? f(Tag<SplitCfg<2, 2, 16, 0, 2>>{}) : f(Tag<SplitCfg<2, 2, 32, 0, 2>>{});
-        }
-        if (s.nt == 1 && s.small) return p16 ? f(Tag<SplitCfg<3, 1, 16, 2, 2>>{}) : f(Tag<SplitCfg<3, 1, 32, 2, 2>>{});
-        if (s.nt == 1) return p16 ? f(Tag<SplitCfg<3, 1, 16, 0, 2>>{}) : f(Tag<SplitCfg<3, 1, 32, 0, 2>>{});
-        return p16 ? f(Tag<SplitCfg<3, 2, 16, 0, 2>>{}) : f(Tag<SplitCfg<3, 2, 32, 0, 2>>{});
-    }
-    return RCF_EUNSUPPORTED;
-}
-
-
-template <class F>
-int dispatch_split(const Sel& s, F&& f) {
-    if (s.bf16) {
-        if (s.kind == K2S1) {
-            if (s.nt == 1) return s.px == 16 ? f(Tag<B2_1_16>{}) : f(Tag<B2_1_32>{});
-            return s.px == 16 ? f(Tag<B2_2_16>{}) : f(Tag<B2_2_32>{});
-        }
-        if (s.kind == K3S2) {
-            if (s.nt == 1) return s.px == 16 ? f(Tag<B3S2_1_16>{}) : f(Tag<B3S2_1_32>{});
-            return s.px == 16 ? f(Tag<B3S2_2_16>{}) : f(Tag<B3S2_2_32>{});
-        }
-        if (s.nt == 1 && s.small) return s.px == 16 ? f(Tag<B3_1_16s>{}) : f(Tag<B3_1_32s>{});
-        if (s.nt == 1) return s.px == 16 ? f(Tag<B3_1_16>{}) : f(Tag<B3_1_32>{});
-        return s.px == 16 ? f(Tag<B3_2_16>{}) : f(Tag<B3_2_32>{});
-    }
-    if constexpr (!SAct::B16) {   // the multi-plane splits exist for fp32 tensors only
-        return s.npl == 2 ? dispatch_split_planes<2>(s, f) : dispatch_split_planes<3>(s, f);
-    }
-    return RCF_EUNSUPPORTED;
 }
 
 // The split weight-gradient kernel addresses a virtual-tall tile through its general path (~3x the address arithmetic per load of
@@ -3258,6 +2936,307 @@ bool wgrad_tr_ok(const rcf_conv_desc* d, const WSel& w) {
     return d->precision == RCF_PREC_F16X2 && (w.kind == K3S1 || w.kind == K2S1);
 }
 
+// ------------------------------------------------------------------------------------------------
+// configuration tables.  One type list per kernel family holds exactly the configurations that are instantiated.  A configuration is
+// found by its key, read from its own members (Fam::key), and dispatch() runs f(Fam, C) on the first match.  The selections
+// (select_cfg / select_wgrad) fill the same key, so rcf_conv2d_query and the launch find the same configuration, or none.
+struct Key {
+    int ks, lstep, px, th;   // taps per kernel row, LDS pixels between neighbouring output pixels, tile (pixels per row, rows)
+    int nt, ck, npl, pm;     // 32-co n-tiles, k-run (FwdCfg; pointwise: all input channels), operand planes (0: the f32 MFMA),
+                             // phase merging (SplitCfg / DmaCfg PM, WsCfg PAIR)
+    int wci, wco;            // weight gradient: 32-channel blocks per workgroup
+    constexpr bool operator==(const Key& o) const {
+        return ks == o.ks && lstep == o.lstep && px == o.px && th == o.th && nt == o.nt && ck == o.ck && npl == o.npl && pm == o.pm &&
+               wci == o.wci && wco == o.wco;
+    }
+};
+
+template <class Fam, class... C>
+struct List {};
+
+template <class... L>
+struct Cat;
+template <class Fam, class... C>
+struct Cat<List<Fam, C...>> { using type = List<Fam, C...>; };
+template <class Fam, class... A, class... B, class... L>
+struct Cat<List<Fam, A...>, List<Fam, B...>, L...> { using type = typename Cat<List<Fam, A..., B...>, L...>::type; };
+
+template <class Fam, class... C>
+constexpr bool keys_unique() {
+    constexpr Key k[] = {Fam::template key<C>()...};
+    for (size_t i = 0; i < sizeof...(C); ++i)
+        for (size_t j = i + 1; j < sizeof...(C); ++j)
+            if (k[i] == k[j]) return false;
+    return true;
+}
+
+template <class Fam, class... C, class F>
+int dispatch(List<Fam, C...>, const Key& key, F&& f) {
+    static_assert(keys_unique<Fam, C...>(), "two configurations of one table have the same key");
+    int rc = RCF_EUNSUPPORTED;
+    (void)(((Fam::template key<C>() == key) && ((rc = f(Fam{}, C{})), true)) || ...);
+    return rc;
+}
+
+// (taps per kernel row, LDS step) of the configurations that run a Kind
+constexpr int kind_ks(int kind) { return kind == K7S2 ? 7 : kind == K4S1 ? 4 : kind == K2S1 ? 2 : kind == K1 ? 1 : 3; }
+constexpr int kind_lstep(int kind) { return (kind == K3S2 || kind == K7S2) ? 2 : 1; }
+
+// ---- forward form.  Every family has grid_x<C> (grid.x = the BN-statistics partial rows the kernel writes) and run<C, E, B>: the
+// plain kernel, its inference epilogue (E: bias, LeakyReLU, residual) or its BatchNorm-backward sums (B), where HAS_EPI /
+// has_bst<C> say that the variant exists.
+template <class Fam>
+struct Tiles {   // the persistent families: one resident wave of workgroups walks the tiles
+    template <class C>
+    static int grid_x(const ConvArgs& a, int ntile_n) {
+        return resident_grid_x<Fam::template kernel<C, false, false>>(C::LDS_BYTES, a.ntiles, ntile_n);
+    }
+    template <class C, bool E, bool B>
+    static int run(const ConvArgs& a, int ntile_n, hipStream_t st) {
+        return launch<Fam::template kernel<C, E, B>>(dim3(grid_x<C>(a, ntile_n), ntile_n, 1), dim3(256), C::LDS_BYTES, st, a);
+    }
+};
+
+struct FwdFam : Tiles<FwdFam> {   // conv_fwd_kernel: the f32 MFMA
+    template <class C> static constexpr Key key() { return {C::KSY, C::LSTEP, C::PX, C::TH, C::NT, C::CK, 0, 0, 0, 0}; }
+    template <class C, bool E, bool B> static constexpr auto kernel = &conv_fwd_kernel<C>;
+    static constexpr bool HAS_EPI = false;
+    template <class C> static constexpr bool has_bst = false;
+};
+
+struct SplitFam : Tiles<SplitFam> {   // conv_split_kernel: fp32 arithmetic on the 16-bit matrix pipe, one to three operand planes
+    template <class C> static constexpr Key key() { return {C::KSY, C::LSTEP, C::PX, C::TH, C::NT, C::CK, C::NPL, C::PM, 0, 0}; }
+    template <class C, bool E, bool B> static constexpr auto kernel = &conv_split_kernel<C, E, SAct, SAct, B>;
+    static constexpr bool HAS_EPI = true;
+    // the BatchNorm-backward sums: fp32 tensors on two fp16 planes, 3x3 stride 1 and 2x2, one output phase
+    template <class C> static constexpr bool has_bst = C::NPL == 2 && C::LSTEP == 1 && !C::P4 && (C::KSY == 3 || C::KSY == 2);
+};
+
+#if RCF_CONV_B16
+struct DmaFam : Tiles<DmaFam> {   // conv_b16_kernel (rcf_conv_b16_dma.h): bf16 tensors, 16-channel chunks reach LDS by DMA
+    template <class C> static constexpr Key key() { return {C::KS, C::LSTEP, C::PX, C::TH, C::NT, 16, 1, C::PM, 0, 0}; }
+    template <class C, bool E, bool B> static constexpr auto kernel = &conv_b16_kernel<C, E, B>;
+    static constexpr bool HAS_EPI = true;
+    // the BatchNorm-backward sums: every 3x3 stride-1 and 2x2 configuration (round 5: the buffer-addressed epilogue freed ~40
+    // registers; the 64-co x 32-pixel-row one had been excluded for its spills)
+    template <class C> static constexpr bool has_bst = C::LSTEP == 1 && !C::P4 && (C::KS == 3 || C::KS == 2);
+};
+
+// grid of the pointwise kernel: x = the BatchNorm partial rows it writes, y walks the output channels 32 * nt at a time
+dim3 pw_dims(const ConvArgs& a, int kst, int nt) {
+    const int gy = ceil_div(a.c_out, 32 * nt);
+    return dim3(pw_grid((long long)a.n * a.h_out * a.w_out, kst, nt, gy), gy);
+}
+#else
+dim3 pw_dims(const ConvArgs& a, int kst, int nt) { return dim3(pw2_grid((long long)a.n * a.h_out * a.w_out, kst, nt)); }
+#endif
+
+// the pointwise (1x1) kernels: operands straight from global memory, the weights in registers, no LDS.  conv1x1_b16_kernel
+// (rcf_conv_b16_dma.h) on bf16 tensors, conv1x1_f16x2_kernel (rcf_conv_pw_f16x2.h) on fp32 tensors in two fp16 planes
+struct PwFam {
+    template <class C> static constexpr Key key() {
+#if RCF_CONV_B16
+        static_assert(C::MT == (C::KST >= 8 ? 1 : (C::NT <= 2 ? 4 : 1)), "pw_mt mirrors PwCfg::MT");
+        return {1, 1, 32, 8, C::NT, 16 * C::KST, 1, 0, 0, 0};
+#else
+        return {1, 1, 32, 8, C::NT, 16 * C::KST, 2, 0, 0, 0};
+#endif
+    }
+#if RCF_CONV_B16
+    template <class C> static constexpr auto kernel = &conv1x1_b16_kernel<C>;
+#else
+    template <class C> static constexpr auto kernel = &conv1x1_f16x2_kernel<C>;
+#endif
+    static constexpr bool HAS_EPI = false;
+    template <class C> static constexpr bool has_bst = false;
+    template <class C> static int grid_x(const ConvArgs& a, int) { return pw_dims(a, C::KST, C::NT).x; }
+    template <class C, bool E, bool B>
+    static int run(const ConvArgs& a, int, hipStream_t st) { return launch<kernel<C>>(pw_dims(a, C::KST, C::NT), dim3(256), 0, st, a); }
+};
+
+//                 KSY KSX XE LS  CK CST STRP NT PX MINW
+using FwdList = List<FwdFam,
+                     FwdCfg<3, 3, 0, 1, 16, 16, 20, 1, 32, 2>, FwdCfg<3, 3, 0, 1, 16, 16, 20, 2, 32, 2>,
+                     FwdCfg<3, 3, 0, 1, 16, 16, 20, 1, 16, 2>, FwdCfg<3, 3, 0, 1, 16, 16, 20, 2, 16, 2>,
+                     FwdCfg<3, 3, 0, 1, 16, 16, 20, 1, 8, 2>, FwdCfg<3, 3, 0, 1, 16, 16, 20, 2, 8, 2>,
+                     FwdCfg<3, 3, 0, 1, 8, 8, 12, 1, 32, 2>, FwdCfg<3, 3, 0, 1, 8, 8, 12, 2, 32, 2>,
+                     FwdCfg<3, 3, 0, 1, 8, 8, 12, 1, 16, 2>, FwdCfg<3, 3, 0, 1, 8, 8, 12, 2, 16, 2>,
+                     FwdCfg<3, 3, 0, 2, 8, 8, 12, 1, 32, 1>, FwdCfg<3, 3, 0, 2, 8, 8, 12, 2, 32, 1>,
+                     FwdCfg<3, 3, 0, 2, 8, 8, 12, 1, 16, 1>, FwdCfg<3, 3, 0, 2, 8, 8, 12, 2, 16, 1>,
+                     FwdCfg<1, 1, 0, 1, 32, 32, 36, 1, 32, 2>, FwdCfg<1, 1, 0, 1, 32, 32, 36, 2, 32, 2>,
+                     FwdCfg<1, 1, 0, 1, 32, 32, 36, 1, 16, 2>, FwdCfg<1, 1, 0, 1, 32, 32, 36, 2, 16, 2>,
+                     FwdCfg<1, 1, 0, 1, 16, 16, 20, 1, 32, 2>, FwdCfg<1, 1, 0, 1, 16, 16, 20, 2, 32, 2>,
+                     FwdCfg<1, 1, 0, 1, 16, 16, 20, 1, 16, 2>, FwdCfg<1, 1, 0, 1, 16, 16, 20, 2, 16, 2>,
+                     FwdCfg<2, 2, 0, 1, 32, 32, 36, 1, 32, 2>, FwdCfg<2, 2, 0, 1, 32, 32, 36, 2, 32, 2>,
+                     FwdCfg<2, 2, 0, 1, 32, 32, 36, 1, 16, 2>, FwdCfg<2, 2, 0, 1, 32, 32, 36, 2, 16, 2>,
+                     FwdCfg<7, 1, 7, 2, 32, 4, 4, 1, 32, 2>, FwdCfg<7, 1, 7, 2, 32, 4, 4, 1, 16, 2>>;
+
+// the split configurations of one operand-plane count: 3x3 stride 1 (32 co: 512-pixel tiles; 64 co and the small layers' 256-pixel x
+// 32-co workgroups: MT 2), 2x2, and 3x3 stride 2 -- 256-pixel tiles with bf16 operands (one plane, two workgroups per CU), 128 on
+// planes (the 65 x 9 halo tile in three planes is 56 KB)
+template <int NPL, int S2MT = NPL == 1 ? 2 : 1>
+using SplitPlanes = List<SplitFam,
+                         SplitCfg<3, 1, 32, 0, NPL>, SplitCfg<3, 2, 32, 0, NPL>, SplitCfg<3, 1, 16, 0, NPL>, SplitCfg<3, 2, 16, 0, NPL>,
+                         SplitCfg<3, 1, 32, 2, NPL>, SplitCfg<3, 1, 16, 2, NPL>,
+                         SplitCfg<2, 1, 32, 0, NPL>, SplitCfg<2, 2, 32, 0, NPL>, SplitCfg<2, 1, 16, 0, NPL>, SplitCfg<2, 2, 16, 0, NPL>,
+                         SplitCfg<3, 1, 32, S2MT, NPL, 2>, SplitCfg<3, 2, 32, S2MT, NPL, 2>, SplitCfg<3, 1, 16, S2MT, NPL, 2>,
+                         SplitCfg<3, 2, 16, S2MT, NPL, 2>>;
+#if RCF_CONV_B16
+using SplitList = SplitPlanes<1>;   // (channel counts that are not multiples of 16: conv_b16_kernel takes the others)
+using DmaList = List<DmaFam,
+                     DmaCfg<3, 2, 32, 2>, DmaCfg<3, 2, 16, 2>,
+                     DmaCfg<3, 1, 32, 4>, DmaCfg<3, 1, 16, 4>,   // 32-co layers: 512-pixel tiles
+                     DmaCfg<3, 1, 32, 2>, DmaCfg<3, 1, 16, 2>,   // small layers: 256-pixel x 32-co workgroups
+                     DmaCfg<2, 2, 32, 2>, DmaCfg<2, 2, 16, 2>, DmaCfg<2, 1, 32, 2>, DmaCfg<2, 1, 16, 2>,
+                     // up-2x forward, four phases from one tile: 256 pixels x 32 co x 4 phases per workgroup, or 128 pixels x 64 co (the
+                     // four accumulator sets are 128 registers either way).  32-pixel tile rows only: the 16-pixel form (per-read LDS
+                     // addresses) spills
+                     DmaCfg<2, 1, 32, 2, 1, 1>, DmaCfg<2, 2, 32, 1, 1, 1>,
+                     DmaCfg<2, 1, 32, 2, 1, 2>, DmaCfg<2, 2, 32, 1, 1, 2>,   // stride-2 input gradient, four output phases from one dz tile
+                     // stride 2: 128-pixel tiles (the 65 x 9 halo tile is 18 KB per buffer)
+                     DmaCfg<3, 2, 32, 1, 2>, DmaCfg<3, 2, 16, 1, 2>, DmaCfg<3, 1, 32, 1, 2>, DmaCfg<3, 1, 16, 1, 2>,
+                     DmaCfg<4, 1, 32, 2>, DmaCfg<4, 1, 16, 2>>;   // the stems: 4x4 on the 16-channel space-to-depth image, <= 32 co
+using PwList = List<PwFam, PwCfg<1, 1>, PwCfg<1, 2>, PwCfg<1, 3>, PwCfg<1, 4>, PwCfg<2, 1>, PwCfg<2, 2>, PwCfg<2, 3>, PwCfg<2, 4>,
+                    PwCfg<3, 1>, PwCfg<3, 2>, PwCfg<4, 1>, PwCfg<4, 2>, PwCfg<4, 3>, PwCfg<8, 1>, PwCfg<8, 2>, PwCfg<16, 1>>;
+#else
+// fp32 tensors: bf16 operands (one plane), exact (three), RCF_PREC_F16X2 (two); on two planes also the stems on the fp32
+// space-to-depth image (4x4 taps, 16 channels, <= 32 co) and the four output phases from one staged tile (32-pixel tile rows; 64 co:
+// 128-pixel tiles -- four accumulator sets)
+using SplitList = Cat<SplitPlanes<1>, SplitPlanes<3>, SplitPlanes<2>,
+                      List<SplitFam, SplitCfg<4, 1, 32, 0, 2>, SplitCfg<4, 1, 16, 0, 2>, SplitCfg<2, 1, 32, 0, 2, 1, 1>,
+                           SplitCfg<2, 2, 32, 1, 2, 1, 1>, SplitCfg<2, 1, 32, 0, 2, 1, 2>, SplitCfg<2, 2, 32, 1, 2, 1, 2>>>::type;
+using PwList = List<PwFam, Pw2Cfg<1, 1>, Pw2Cfg<1, 2>, Pw2Cfg<1, 3>, Pw2Cfg<1, 4>, Pw2Cfg<2, 1>, Pw2Cfg<2, 2>, Pw2Cfg<2, 3>,
+                    Pw2Cfg<2, 4>, Pw2Cfg<3, 1>, Pw2Cfg<3, 2>, Pw2Cfg<4, 1>, Pw2Cfg<4, 2>>;
+#endif
+
+// rcf_conv_info.fwd_act: the inference epilogue (a family with HAS_EPI) on a plain forward convolution
+bool fwd_act_ok(const rcf_conv_desc* d) { return d->w_mode == RCF_W_FORWARD && !d->accumulate; }
+
+// rcf_conv_info.bn_bwd_sums: may this descriptor's launch take the BatchNorm-backward sums of the block whose output gradient it
+// writes?  It must write every element of a plain NHWC tensor exactly once (or add to it as the LAST writer: the caller's business),
+// on a configuration with the variant (has_bst), with one source (an input gradient has one) and no statistics of its own (not
+// accumulating: the launch is the only writer of dY -- the kernels' BatchNorm-sums variants contain no += path)
+bool bn_sums_ok(const rcf_conv_desc* d) {
+    return d->c2 == 0 && d->out_stride == 1 && d->out_off_y == 0 && d->out_off_x == 0 && d->out_h_phys == d->h_out &&
+           d->out_w_phys == d->w_out && d->accumulate == 0;
+}
+
+// The forward form (fwd / fwd_bn / fwd_scaled / dgrad_bn_sums / fwd_act) of a selection: f(Fam, C) on the family and configuration
+// that run it, or RCF_EUNSUPPORTED.  rcf_conv2d_query and conv2d_fwd_impl both decide through here.
+template <class F>
+int with_fwd_cfg(const rcf_conv_desc* d, const Sel& s, F&& f) {
+    const Key k = {kind_ks(s.kind), kind_lstep(s.kind), s.px, s.th, s.nt, s.pw ? d->c1 : s.ck, s.split ? s.npl : 0, s.p4, 0, 0};
+    if (s.pw) return dispatch(PwList{}, k, f);
+#if RCF_CONV_B16
+    if (s.dma) return dispatch(DmaList{}, k, f);
+#endif
+    return s.split ? dispatch(SplitList{}, k, f) : dispatch(FwdList{}, k, f);
+}
+
+// ---- weight gradient.  run<C>(a, w, st) launches the partial sums (conv2d_wgrad_impl reduces them); TR: the transposing-read kernel
+struct WgFam {   // conv_wgrad_kernel (register-staged) / conv_wgrad_dma_kernel (fp32 tensors, 4-aligned channels: LDS-DMA staging)
+    template <class C> static constexpr Key key() { return {C::KSY, C::LSTEP, C::PX, C::TH, 0, 0, 0, 0, 1, 1}; }
+    static constexpr bool TR = false;
+    template <class C> static constexpr int dma_lds() {
+        using H = Halo<C::CST, C::STRP, C::HXP, C::HYP>;
+        constexpr int red_floats = C::T * 16 * 64;
+        constexpr int tile_floats = H::NA * H::PPI * 32 + C::TP * 32;
+        return (tile_floats > red_floats ? tile_floats : red_floats) * 4;
+    }
+    template <class C>
+    static int run(const ConvArgs& a, const WSel& w, hipStream_t st) {
+        const dim3 grid(w.nsplit, w.nchunk1 + w.nchunk2, w.ncog);
+        if constexpr (!SAct::B16 && C::KSY != 7)   // (LDS-DMA copies fp32 tiles verbatim; the 7x7 stem stages its channels 4 wide)
+            if (a.c1 % 4 == 0 && a.c2 % 4 == 0) return launch<&conv_wgrad_dma_kernel<C>>(grid, dim3(256), dma_lds<C>(), st, a);
+        if constexpr (C::PX != 8) return launch<&conv_wgrad_kernel<C>>(grid, dim3(256), C::LDS_BYTES, st, a);
+        return RCF_EUNSUPPORTED;   // (8-pixel rows exist on the DMA kernel only)
+    }
+};
+
+struct WsFam {   // conv_wgrad_split_kernel: fp32 arithmetic on the 16-bit matrix pipe, one to three operand planes
+    template <class C> static constexpr Key key() { return {C::KS, 1, C::PX, C::TH, 0, 0, C::NPL, C::PAIR, C::WCI, C::WCO}; }
+    static constexpr bool TR = false;
+    template <class C>
+    static int run(const ConvArgs& a, const WSel& w, hipStream_t st) {
+        return launch<&conv_wgrad_split_kernel<C>>(dim3(w.nsplit, w.gy, w.gz), dim3(256), C::LDS_BYTES, st, a);
+    }
+};
+
+struct WtFam {   // conv_wgrad_tr_kernel (rcf_conv_wgrad_tr.h): producer / consumer waves, transposing LDS reads
+    template <class C> static constexpr Key key() {
+        static_assert(C::PX == 16, "wgrad_kernel_id: the transposing kernel's +200 is unambiguous on 16-pixel tile rows only");
+        return {C::KS, 1, C::PX, C::TH, 0, 0, C::NPL, 0, C::WCI, C::WCO};
+    }
+    static constexpr bool TR = true;
+    template <class C>
+    static int run(const ConvArgs& a, const WSel& w, hipStream_t st) {
+        return launch<&conv_wgrad_tr_kernel<C>>(dim3(w.nsplit, w.gy, w.gz), dim3(512), C::template lds_bytes<SAct::B16>(), st, a);
+    }
+};
+
+//                 KSY KSX XE LS CST STRP PX TH MINW
+using WgList = List<WgFam,
+#if !RCF_CONV_B16
+                    WgCfg<3, 3, 0, 1, 32, 32, 8, 32, 1>,   // (8-pixel rows: fp32 tensors, the DMA kernel)
+#endif
+                    WgCfg<3, 3, 0, 1, 32, 32, 32, 8, 1>, WgCfg<3, 3, 0, 1, 32, 32, 16, 16, 1>,
+                    WgCfg<3, 3, 0, 2, 32, 32, 32, 4, 1>, WgCfg<3, 3, 0, 2, 32, 32, 16, 8, 1>,
+                    WgCfg<1, 1, 0, 1, 32, 32, 32, 8, 2>, WgCfg<1, 1, 0, 1, 32, 32, 16, 16, 2>,
+                    WgCfg<2, 2, 0, 1, 32, 32, 32, 8, 1>, WgCfg<2, 2, 0, 1, 32, 32, 16, 16, 1>,
+                    WgCfg<7, 1, 7, 2, 4, 4, 32, 8, 2>, WgCfg<7, 1, 7, 2, 4, 4, 16, 16, 2>>;
+
+// the four channel blockings of the split weight-gradient kernels (64 / 32 input x 64 / 32 output channels per workgroup) for one
+// (taps, operand planes): WTH tile rows, 16 for 32 x 32 (select_wgrad: th_split)
+constexpr int WTH = SAct::B16 ? 16 : 8;
+template <int KS, int NPL, bool PAIR = false>
+using WsQuad = List<WsFam, WsCfg<2, 2, KS, WTH, NPL, PAIR>, WsCfg<1, 2, KS, WTH, NPL, PAIR>, WsCfg<2, 1, KS, WTH, NPL, PAIR>,
+                    WsCfg<1, 1, KS, 16, NPL, PAIR>>;
+template <int KS, int NPL>
+using WtQuad = List<WtFam, WtCfg<2, 2, KS, WTH, NPL>, WtCfg<1, 2, KS, WTH, NPL>, WtCfg<2, 1, KS, WTH, NPL>, WtCfg<1, 1, KS, 16, NPL>>;
+#if RCF_CONV_B16
+using WsList = Cat<WsQuad<3, 1>, WsQuad<2, 1>, WsQuad<2, 1, true>, WsQuad<1, 1>>::type;
+using WtList = Cat<WtQuad<3, 1>, WtQuad<2, 1>, WtQuad<1, 1>>::type;
+#else
+using WsList = Cat<WsQuad<3, 1>, WsQuad<2, 1>, WsQuad<2, 1, true>, WsQuad<3, 2>, WsQuad<2, 2>, WsQuad<2, 2, true>, WsQuad<3, 3>,
+                   WsQuad<2, 3>>::type;
+using WtList = Cat<WtQuad<3, 2>, WtQuad<2, 2>>::type;
+#endif
+
+// operand planes of a split weight gradient: 1 (RCF_PREC_BF16), 2 (RCF_PREC_F16X2), 3 (exact)
+int wgrad_planes(const rcf_conv_desc* d) { return d->precision == RCF_PREC_BF16 ? 1 : (d->precision == RCF_PREC_F16X2 ? 2 : 3); }
+
+// The weight gradient of a selection: f(Fam, C) on the family and configuration that run it, or RCF_EUNSUPPORTED.  BatchNorm-on-load
+// (bn) keeps conv_wgrad_split_kernel.  rcf_conv2d_query (bn = false) and conv2d_wgrad_impl both decide through here.
+template <class F>
+int with_wgrad_cfg(const rcf_conv_desc* d, const WSel& w, bool bn, F&& f) {
+    const Key k = {kind_ks(w.kind), kind_lstep(w.kind), w.px, w.th, 0, 0, w.split ? wgrad_planes(d) : 0,
+                   (w.split && wgrad_phase_pairs(d)) ? 1 : 0, w.wci, w.wco};
+    if (!w.split) return dispatch(WgList{}, k, f);
+    return (wgrad_tr_ok(d, w) && !bn) ? dispatch(WtList{}, k, f) : dispatch(WsList{}, k, f);
+}
+
+// rcf_conv_info.kernel_id (bench.py, engine.py and the tests decode it).  The stem on the space-to-depth image reports kind 3 like the
+// 7x7 stem it stands for: 3000 + 5000 (split) stays below the weight-gradient ids, 10000 + ...
+int kernel_id(const Sel& s) {
+    return (s.kind == K4S1 ? (int)K7S2 : s.kind) * 1000 + s.ck * 10 + s.nt + (s.px == 16 ? 100 : (s.px == 8 ? 200 : 0)) + (s.vt ? 400 : 0) +
+           (s.split ? 5000 : 0) + (s.small ? 5 : 0) + (s.bf16 ? 20000 : 0) + ((s.split && s.npl == 2) ? 40000 : 0);
+}
+
+// rcf_conv_info.wgrad_kernel_id.  The transposing-read kernel (tr) adds 200, the digit of px == 8: unambiguous because that kernel
+// tiles 16-pixel rows only (WtFam::key)
+int wgrad_kernel_id(const rcf_conv_desc* d, const WSel& w, bool tr) {
+    if (tr && w.px != 16) return RCF_EUNSUPPORTED;
+    return 10000 + w.kind * 1000 + (w.px == 16 ? 100 : (w.px == 8 ? 200 : 0)) + (w.vt ? 400 : 0) + (tr ? 200 : 0) +
+           (w.split ? 5000 + w.wci * 10 + w.wco : 0) + ((w.split && d->precision == RCF_PREC_BF16) ? 20000 : 0) +
+           ((w.split && d->precision == RCF_PREC_F16X2) ? 40000 : 0);
+}
+
+// floats of the packed weights: [n-tile][chunk][tap][BN] rows of CK floats (the f32 MFMA) or of 16 bf16 per operand plane (split)
+size_t packed_floats(const rcf_conv_desc* d, const Sel& s) {
+    const int nchunk = ceil_div(d->c1, s.cst) + (d->c2 > 0 ? ceil_div(d->c2, s.cst) : 0);
+    return (size_t)ceil_div(d->c_out, s.bn) * nchunk * s.t * s.bn * (s.split ? 8 * s.npl : s.ck);
+}
+
 }   // namespace
 
 // ---- entry points.  The fp32 unit owns the public names and hands descriptors with storage == RCF_STORE_BF16 to the bf16 unit.
@@ -3336,15 +3315,6 @@ extern "C" int rcf_phase_wgrad_gather_s2(const float* dwp, float* dw_oihw, int o
 }
 #endif
 
-// may this descriptor's launch take the BatchNorm-backward sums of the block whose output gradient it writes?  It must write every
-// element of a plain NHWC tensor exactly once (or add to it as the LAST writer: the caller's business), on a kernel that has the
-// epilogue (split_bst_ok), with one source (an input gradient has one) and no statistics of its own
-static bool bn_sums_ok(const rcf_conv_desc* d, const Sel& s) {
-    // (not accumulating: the launch is the only writer of dY -- the kernels' BatchNorm-sums variants contain no += path)
-    return split_bst_ok(s) && d->c2 == 0 && d->out_stride == 1 && d->out_off_y == 0 && d->out_off_x == 0 &&
-           d->out_h_phys == d->h_out && d->out_w_phys == d->w_out && d->accumulate == 0;
-}
-
 extern "C" int RCF_FN(rcf_conv2d_query)(const rcf_conv_desc* d, rcf_conv_info* info) {
     RCF_TO_B16(d, rcf_conv2d_query_b16impl(d, info));
     if (!info) return RCF_EINVAL;
@@ -3353,30 +3323,27 @@ extern "C" int RCF_FN(rcf_conv2d_query)(const rcf_conv_desc* d, rcf_conv_info* i
     if (rc != RCF_OK) return rc;
     ConvArgs a;
     fill_args(d, s, &a);
-    const int ntile_n = ceil_div(d->c_out, s.bn);
-    info->packed_weight_floats = (size_t)ntile_n * (a.nchunk1 + a.nchunk2) * s.t * s.bn * s.ck;
-    if (s.split) info->packed_weight_floats = (size_t)ntile_n * (a.nchunk1 + a.nchunk2) * s.t * s.bn * 8 * s.npl;   // 16 bf16 x planes per row
-#if !RCF_CONV_B16
-    if (s.pw) info->n_partials = pw2_grid((long long)d->n * d->h_out * d->w_out, d->c1 / 16, s.nt);
-    else
-#endif
-#if RCF_CONV_B16
-    if (s.pw) info->n_partials = pw_grid((long long)d->n * d->h_out * d->w_out, d->c1 / 16, s.nt, ceil_div(d->c_out, 32 * s.nt));
-    else if (s.dma) info->n_partials = dispatch_dma(s, [&](auto tag) { return dma_grid_x<typename decltype(tag)::type>(a.ntiles, ntile_n); });
-    else
-#endif
-    info->n_partials = s.split ? dispatch_split(s, [&](auto tag) { return split_grid_x<typename decltype(tag)::type>(a.ntiles, ntile_n); })
-                               : dispatch_fwd(s, [&](auto tag) { return fwd_grid_x<typename decltype(tag)::type>(a.ntiles, ntile_n); });
-    if (info->n_partials <= 0) return RCF_EUNSUPPORTED;
-    // (the stem on the space-to-depth image reports kind 3 like the 7x7 stem it stands for: 3000 + 5000 (split) stays below the
-    // weight-gradient ids, 10000 + ...)
-    info->kernel_id = (s.kind == K4S1 ? (int)K7S2 : s.kind) * 1000 + s.ck * 10 + s.nt + (s.px == 16 ? 100 : (s.px == 8 ? 200 : 0)) + (s.vt ? 400 : 0) + (s.split ? 5000 : 0) + (s.small ? 5 : 0) + (s.bf16 ? 20000 : 0) + ((s.split && s.npl == 2) ? 40000 : 0);
+    info->packed_weight_floats = packed_floats(d, s);
+    info->fwd_act = 0;
+    info->bn_bwd_sums = 0;
+    if (s.pw) {   // (from the selection: PwCfg has no (3, 3) / (3, 4) entry, and the launch of those answers RCF_EUNSUPPORTED)
+        info->n_partials = pw_dims(a, d->c1 / 16, s.nt).x;
+    } else {
+        rc = with_fwd_cfg(d, s, [&](auto fam, auto c) {
+            using Fam = decltype(fam);
+            using C = decltype(c);
+            info->n_partials = Fam::template grid_x<C>(a, ceil_div(d->c_out, s.bn));
+            info->fwd_act = (Fam::HAS_EPI && fwd_act_ok(d)) ? 1 : 0;
+            info->bn_bwd_sums = (Fam::template has_bst<C> && bn_sums_ok(d)) ? 1 : 0;
+            return RCF_OK;
+        });
+        if (rc != RCF_OK) return rc;
+    }
+    info->kernel_id = kernel_id(s);
     info->wgrad_workspace_floats = 0;
     info->wgrad_kernel_id = 0;
     info->bn_on_load = (s.split && !s.dma && !s.pw && d->w_mode == RCF_W_FORWARD && d->c1 + d->c2 <= 512 && s.npl != 2) ? 1 : 0;   // a DMA cannot transform; fp16 planes need the maximum of the TRANSFORMED tensor
     info->wgrad_bn_on_load = 0;
-    info->fwd_act = (s.split && !s.pw && d->w_mode == RCF_W_FORWARD && !d->accumulate) ? 1 : 0;
-    info->bn_bwd_sums = bn_sums_ok(d, s) ? 1 : 0;
     if (d->w_mode == RCF_W_FORWARD) {
         WSel w;
         if (select_wgrad(d, &w) == RCF_OK) {
@@ -3384,9 +3351,9 @@ extern "C" int RCF_FN(rcf_conv2d_query)(const rcf_conv_desc* d, rcf_conv_info* i
             const int nrows = (d->phase_sum == 1 || d->phase_sum == 2) ? 4 * wgrad_phase_slots(w.nsplit, d) : w.nsplit;
             info->wgrad_workspace_floats = (size_t)nrows * w.ktot * w.cop + 64;   // + a zero page for the DMA path
             info->wgrad_bn_on_load = (w.split && !SAct::B16 && d->precision != RCF_PREC_F16X2) ? 1 : 0;   // bf16 tensors are staged raw: nothing to apply BatchNorm to
-            info->wgrad_kernel_id = 10000 + w.kind * 1000 + (w.px == 16 ? 100 : (w.px == 8 ? 200 : 0)) + (w.vt ? 400 : 0) + (wgrad_tr_ok(d, w) ? 200 : 0) +
-                                    (w.split ? 5000 + w.wci * 10 + w.wco : 0) + ((w.split && d->precision == RCF_PREC_BF16) ? 20000 : 0) +
-                                    ((w.split && d->precision == RCF_PREC_F16X2) ? 40000 : 0);
+            rc = with_wgrad_cfg(d, w, false, [&](auto fam, auto) { return wgrad_kernel_id(d, w, decltype(fam)::TR); });
+            if (rc < 0) return rc;
+            info->wgrad_kernel_id = rc;
         }
     }
     return RCF_OK;
@@ -3400,13 +3367,12 @@ static int pack_args(const rcf_conv_desc* d, const float* w_oihw, float* packed,
     if (rc != RCF_OK) return rc;
     ConvArgs a;
     fill_args(d, s, &a);
-    const int ntile_n = ceil_div(d->c_out, s.bn);
     const int nchunk = a.nchunk1 + a.nchunk2;
     p->w = w_oihw; p->dst = packed; p->amax = amax_w;
     p->w_o = d->w_o; p->w_i = d->w_i; p->ks = d->ksize; p->mode = d->w_mode; p->i_off = d->w_i_off; p->c_out = d->c_out;
     p->c1 = d->c1; p->c2 = d->c2; p->nchunk1 = a.nchunk1; p->nchunk = nchunk; p->T = s.t; p->BN = s.bn; p->CK = s.ck;
     p->ksx = s.kind == K7S2 ? 1 : d->ksize; p->kind = s.kind == K7S2 ? 1 : 0; p->npl = s.npl; p->split = s.split ? 1 : 0;
-    p->total = s.split ? (unsigned long long)ntile_n * nchunk * s.t * s.bn * 16 : (unsigned long long)ntile_n * nchunk * s.t * s.bn * s.ck;
+    p->total = s.split ? packed_floats(d, s) / s.npl * 2 : packed_floats(d, s);   // split: bf16 elements of one plane
     *blocks = (unsigned)((p->total + 255) / 256);
     return RCF_OK;
 }
@@ -3480,9 +3446,12 @@ extern "C" int RCF_FN(rcf_conv2d_pack_weights_batch)(const rcf_pack_item* items,
     return rcf_launch_status();
 }
 
+// the forward form: coef1 / coef2 BatchNorm-on-load, sc the two-plane scales, bn_z / bn_coef the BatchNorm-backward sums
+// (rcf_conv_info.bn_bwd_sums), bias / res the inference epilogue (rcf_conv_info.fwd_act)
 static int conv2d_fwd_impl(const rcf_conv_desc* d, const float* in1, const float* coef1, const float* in2, const float* coef2,
                            const float* packed, float* out, double* stat_partials, void* stream, const rcf_conv_scales* sc = nullptr,
-                           const float* bn_z = nullptr, const float* bn_coef = nullptr);
+                           const float* bn_z = nullptr, const float* bn_coef = nullptr, const float* bias = nullptr,
+                           const float* res = nullptr);
 
 extern "C" int RCF_FN(rcf_conv2d_fwd)(const rcf_conv_desc* d, const void* in1, const void* in2, const float* packed, void* out,
                                       double* stat_partials, void* stream) {
@@ -3519,113 +3488,52 @@ extern "C" int RCF_FN(rcf_conv2d_dgrad_bn_sums)(const rcf_conv_desc* d, const vo
                            (const float*)bn_z, bn_coef);
 }
 
+extern "C" int RCF_FN(rcf_conv2d_fwd_act)(const rcf_conv_desc* d, const void* in1, const void* in2, const float* packed,
+                                          const float* bias, const void* res, void* out, void* stream) {
+    RCF_TO_B16(d, rcf_conv2d_fwd_act_b16impl(d, in1, in2, packed, bias, res, out, stream));
+    if (!bias) return RCF_EINVAL;
+    return conv2d_fwd_impl(d, (const float*)in1, nullptr, (const float*)in2, nullptr, packed, (float*)out, nullptr, stream, nullptr,
+                           nullptr, nullptr, bias, (const float*)res);
+}
+
 static int conv2d_fwd_impl(const rcf_conv_desc* d, const float* in1, const float* coef1, const float* in2, const float* coef2,
                            const float* packed, float* out, double* stat_partials, void* stream, const rcf_conv_scales* sc,
-                           const float* bn_z, const float* bn_coef) {
+                           const float* bn_z, const float* bn_coef, const float* bias, const float* res) {
     if (!in1 || !packed || !out) return RCF_EINVAL;
     Sel s;
     int rc = select_cfg(d, &s);
     if (rc != RCF_OK) return rc;
     if (d->c2 > 0 && !in2) return RCF_EINVAL;
-    if ((coef1 || coef2) && (!s.split || d->w_mode != RCF_W_FORWARD || d->c1 + d->c2 > 512 || (coef2 && d->c2 == 0)))
-        return RCF_EUNSUPPORTED;   // BN-on-load exists in the split kernels only (rcf_conv_info.bn_on_load)
+    // BN-on-load exists in the split kernels only, and not in the DMA / pointwise ones (rcf_conv_info.bn_on_load)
+    if ((coef1 || coef2) && (!s.split || s.dma || s.pw || d->w_mode != RCF_W_FORWARD || d->c1 + d->c2 > 512 || (coef2 && d->c2 == 0)))
+        return RCF_EUNSUPPORTED;
+    if (sc != nullptr && (!s.split || s.npl != 2)) return RCF_EUNSUPPORTED;   // scales belong to the two-plane fp16 split kernels
     ConvArgs a;
     fill_args(d, s, &a);
     if (a.zero == nullptr) return (int)hipErrorInvalidSymbol;
-    a.coef1 = coef1; a.coef2 = coef2;
-    a.in1 = in1; a.in2 = in2; a.wp = packed; a.out = out; a.stats = stat_partials; a.dz = nullptr; a.ws = nullptr;
-    a.ktot = 0; a.cop = 0;
-    if (sc != nullptr) {
-        if (!s.split || s.npl != 2) return RCF_EUNSUPPORTED;   // scales belong to the two-plane fp16 split kernels
-        a.amax_a1 = sc->amax_in1; a.amax_a2 = d->c2 > 0 ? sc->amax_in2 : nullptr; a.amax_b = sc->amax_w;
-    }
+    a.coef1 = coef1; a.coef2 = coef2; a.bias = bias; a.res = res; a.bz = bn_z; a.bk = bn_coef;
+    a.in1 = in1; a.in2 = in2; a.wp = packed; a.out = out; a.stats = stat_partials;
+    if (sc != nullptr) { a.amax_a1 = sc->amax_in1; a.amax_a2 = d->c2 > 0 ? sc->amax_in2 : nullptr; a.amax_b = sc->amax_w; }
+    a.wp_phase_stride = (int)packed_floats(d, s);
+#ifdef RCF_B16_DIAG
+    { const char* dg = getenv("RCF_B16_DIAG"); if (s.dma && !bn_z && dg && dg[0] == '1') a.xcd_band += 64; }
+#endif
     const int nn = ceil_div(d->c_out, s.bn);
-    a.wp_phase_stride = (int)((size_t)nn * (a.nchunk1 + a.nchunk2) * s.t * s.bn * (s.split ? 8 * s.npl : s.ck));
-#if RCF_CONV_B16
-    if (s.pw) {
-        if (coef1 || coef2) return RCF_EUNSUPPORTED;
-        return dispatch_pw(d->c1 / 16, s.nt, [&](auto cfg) { return launch_pw<decltype(cfg)>(a, (hipStream_t)stream); });
-    }
-    if (s.dma && bn_z != nullptr) {   // rcf_conv_info.bn_bwd_sums
-        if (!bn_sums_ok(d, s) || coef1 || coef2) return RCF_EUNSUPPORTED;
-        a.bz = bn_z; a.bk = bn_coef;
-        const bool p16 = s.px == 16;
-        hipStream_t st = (hipStream_t)stream;
-        if (s.kind == K2S1) {
-            if (s.nt == 1) return p16 ? launch_dma_bst<D2_1_16>(a, nn, st) : launch_dma_bst<D2_1_32>(a, nn, st);
-            return p16 ? launch_dma_bst<D2_2_16>(a, nn, st) : launch_dma_bst<D2_2_32>(a, nn, st);
+    return with_fwd_cfg(d, s, [&](auto fam, auto c) -> int {
+        using Fam = decltype(fam);
+        using C = decltype(c);
+        if (bias) {   // rcf_conv_info.fwd_act
+            if constexpr (Fam::HAS_EPI)
+                if (fwd_act_ok(d)) return Fam::template run<C, true, false>(a, nn, (hipStream_t)stream);
+            return RCF_EUNSUPPORTED;
         }
-        if (s.nt == 1 && s.small) return p16 ? launch_dma_bst<D3_1_16s>(a, nn, st) : launch_dma_bst<D3_1_32s>(a, nn, st);
-        if (s.nt == 1) return p16 ? launch_dma_bst<D3_1_16>(a, nn, st) : launch_dma_bst<D3_1_32>(a, nn, st);
-        return p16 ? launch_dma_bst<D3_2_16>(a, nn, st) : launch_dma_bst<D3_2_32>(a, nn, st);
-    }
-    if (s.dma && !coef1 && !coef2)
-        return dispatch_dma(s, [&](auto tag) { return launch_dma<typename decltype(tag)::type, false>(a, nn, (hipStream_t)stream); });
-    if (s.dma) return RCF_EUNSUPPORTED;   // rcf_conv_info.bn_on_load is 0 for these descriptors (the tile geometry differs)
-#endif
-    if (s.kind == K4S1 && SAct::B16) return RCF_EUNSUPPORTED;
-#if !RCF_CONV_B16
-    if (s.pw) {
-        if (coef1 || coef2 || bn_z) return RCF_EUNSUPPORTED;
-        return dispatch_pw2(d->c1 / 16, s.nt, [&](auto cfg) { return launch_pw2<decltype(cfg)>(a, (hipStream_t)stream); });
-    }
-#endif
-    if (bn_z != nullptr) {   // rcf_conv_info.bn_bwd_sums: an input-gradient launch over a plain (unit-stride, whole) output tensor
-        if (!bn_sums_ok(d, s)) return RCF_EUNSUPPORTED;
-        a.bz = bn_z; a.bk = bn_coef;
-        return dispatch_split_bst(s, [&](auto tag) { return launch_split_bst<typename decltype(tag)::type>(a, nn, (hipStream_t)stream); });
-    }
-    if (s.split) return dispatch_split(s, [&](auto tag) { return launch_split<typename decltype(tag)::type>(a, nn, (hipStream_t)stream); });
-    return dispatch_fwd(s, [&](auto tag) { return launch_fwd<typename decltype(tag)::type>(a, nn, (hipStream_t)stream); });
-}
-
-extern "C" int RCF_FN(rcf_conv2d_fwd_act)(const rcf_conv_desc* d, const void* in1_, const void* in2_, const float* packed,
-                                          const float* bias, const void* res_, void* out_, void* stream) {
-    RCF_TO_B16(d, rcf_conv2d_fwd_act_b16impl(d, in1_, in2_, packed, bias, res_, out_, stream));
-    const float* in1 = (const float*)in1_;
-    const float* in2 = (const float*)in2_;
-    const float* res = (const float*)res_;
-    float* out = (float*)out_;
-    if (!in1 || !packed || !out || !bias) return RCF_EINVAL;
-    Sel s;
-    int rc = select_cfg(d, &s);
-    if (rc != RCF_OK) return rc;
-    if (d->c2 > 0 && !in2) return RCF_EINVAL;
-    if (!s.split || s.pw || d->w_mode != RCF_W_FORWARD || d->accumulate) return RCF_EUNSUPPORTED;   // rcf_conv_info.fwd_act
-    ConvArgs a;
-    fill_args(d, s, &a);
-    if (a.zero == nullptr) return (int)hipErrorInvalidSymbol;
-    a.bias = bias; a.res = res;
-    a.in1 = in1; a.in2 = in2; a.wp = packed; a.out = out; a.stats = nullptr; a.dz = nullptr; a.ws = nullptr;
-    a.ktot = 0; a.cop = 0;
-    const int nn = ceil_div(d->c_out, s.bn);
-    a.wp_phase_stride = (int)((size_t)nn * (a.nchunk1 + a.nchunk2) * s.t * s.bn * 8 * s.npl);
-#if RCF_CONV_B16
-    if (s.dma) return dispatch_dma(s, [&](auto tag) { return launch_dma<typename decltype(tag)::type, true>(a, nn, (hipStream_t)stream); });
-#endif
-    return dispatch_split(s, [&](auto tag) { return launch_split<typename decltype(tag)::type, true>(a, nn, (hipStream_t)stream); });
-}
-
-// split weight-gradient kernels on fp32 tensors: NPL = 3 (exact) or 2 (RCF_PREC_F16X2); same tilings (select_wgrad)
-template <int NPL>
-static int launch_wgrad_split_planes(const ConvArgs& a, const WSel& w, int cfg, hipStream_t st) {
-    if constexpr (NPL == 2)
-    if (w.kind == K2S1 && a.phase_sum == 2) {   // the up-2x weight gradient: phase pairs from one x tile
-        if (cfg == 22) return launch_wgrad_split<WsCfg<2, 2, 2, 8, NPL, true>>(a, w.nsplit, w.gy, w.gz, st);
-        if (cfg == 12) return launch_wgrad_split<WsCfg<1, 2, 2, 8, NPL, true>>(a, w.nsplit, w.gy, w.gz, st);
-        if (cfg == 21) return launch_wgrad_split<WsCfg<2, 1, 2, 8, NPL, true>>(a, w.nsplit, w.gy, w.gz, st);
-        return launch_wgrad_split<WsCfg<1, 1, 2, 16, NPL, true>>(a, w.nsplit, w.gy, w.gz, st);
-    }
-    if (w.kind == K2S1) {
-        if (cfg == 22) return launch_wgrad_split<WsCfg<2, 2, 2, 8, NPL>>(a, w.nsplit, w.gy, w.gz, st);
-        if (cfg == 12) return launch_wgrad_split<WsCfg<1, 2, 2, 8, NPL>>(a, w.nsplit, w.gy, w.gz, st);
-        if (cfg == 21) return launch_wgrad_split<WsCfg<2, 1, 2, 8, NPL>>(a, w.nsplit, w.gy, w.gz, st);
-        return launch_wgrad_split<WsCfg<1, 1, 2, 16, NPL>>(a, w.nsplit, w.gy, w.gz, st);
-    }
-    if (cfg == 22) return launch_wgrad_split<WsCfg<2, 2, 3, 8, NPL>>(a, w.nsplit, w.gy, w.gz, st);
-    if (cfg == 12) return launch_wgrad_split<WsCfg<1, 2, 3, 8, NPL>>(a, w.nsplit, w.gy, w.gz, st);
-    if (cfg == 21) return launch_wgrad_split<WsCfg<2, 1, 3, 8, NPL>>(a, w.nsplit, w.gy, w.gz, st);
-    return launch_wgrad_split<WsCfg<1, 1, 3, 16, NPL>>(a, w.nsplit, w.gy, w.gz, st);
+        if (bn_z) {   // rcf_conv_info.bn_bwd_sums
+            if constexpr (Fam::template has_bst<C>)
+                if (bn_sums_ok(d)) return Fam::template run<C, false, true>(a, nn, (hipStream_t)stream);
+            return RCF_EUNSUPPORTED;
+        }
+        return Fam::template run<C, false, false>(a, nn, (hipStream_t)stream);
+    });
 }
 
 static int conv2d_wgrad_impl(const rcf_conv_desc* d, const float* in1, const float* coef1, const float* in2, const float* coef2,
@@ -3659,27 +3567,18 @@ static int conv2d_wgrad_impl(const rcf_conv_desc* d, const float* in1, const flo
     int rc = select_wgrad(d, &w);
     if (rc != RCF_OK) return rc;
     if (d->c2 > 0 && !in2) return RCF_EINVAL;
-    if ((coef1 || coef2) && (!w.split || SAct::B16 || (coef2 && d->c2 == 0))) return RCF_EUNSUPPORTED;
+    const bool bn = coef1 || coef2;
+    if (bn && (!w.split || SAct::B16 || (coef2 && d->c2 == 0))) return RCF_EUNSUPPORTED;
+    if (sc != nullptr && (!w.split || d->precision != RCF_PREC_F16X2)) return RCF_EUNSUPPORTED;
     ConvArgs a;
-    a.xcd_band = 0;
-    a.bias = nullptr; a.res = nullptr;
-    a.amax_a1 = nullptr; a.amax_a2 = nullptr; a.amax_b = nullptr;
-    a.bz = nullptr; a.bk = nullptr;
-    if (sc != nullptr) {
-        if (!w.split || d->precision != RCF_PREC_F16X2) return RCF_EUNSUPPORTED;
-        a.amax_a1 = sc->amax_in1; a.amax_a2 = d->c2 > 0 ? sc->amax_in2 : nullptr; a.amax_b = sc->amax_dz;
-    }
-    a.zero = zero_page_ptr();
+    fill_args(d, w, &a);
     if (a.zero == nullptr) return (int)hipErrorInvalidSymbol;
-    a.coef1 = coef1; a.coef2 = coef2;
-    a.n = d->n; a.h_in = d->h_in; a.w_in = d->w_in; a.c1 = d->c1; a.c2 = d->c2;
-    a.h1 = d->h_src1; a.w1 = d->w_src1; a.gather1 = d->gather1;
-    a.h_out = d->h_out; a.w_out = d->w_out; a.c_out = d->c_out; a.pad = d->pad; a.pad_x = d->pad_x; a.stride = d->stride;
-    a.gstep = d->ksize == 1 ? d->stride : 1;
+    a.xcd_band = 0;
     a.accumulate = 0;
-    a.os = d->out_stride; a.ooy = d->out_off_y; a.oox = d->out_off_x; a.ohp = d->out_h_phys; a.owp = d->out_w_phys;
-    a.ioy = d->in_off_y; a.iox = d->in_off_x;
-    a.phase_sum = 0; a.wp_phase_stride = 0;
+    a.coef1 = coef1; a.coef2 = coef2;
+    if (sc != nullptr) { a.amax_a1 = sc->amax_in1; a.amax_a2 = d->c2 > 0 ? sc->amax_in2 : nullptr; a.amax_b = sc->amax_dz; }
+    a.in1 = in1; a.in2 = in2; a.dz = dz; a.ws = workspace;
+    a.ktot = w.ktot; a.cop = w.cop;
     // phase_sum == 2 (the merged up-2x forward descriptor): the four phases' weight gradients in one launch of the split kernel, into
     // dw[4][c_out][c_in][2][2]; each phase keeps its own workspace rows and its own reduction
     // phase_sum == 1 on a RCF_GATHER_STRIDED2 descriptor (in_off_* ignored): the four phase weight gradients of a 3x3 stride-2
@@ -3688,20 +3587,8 @@ static int conv2d_wgrad_impl(const rcf_conv_desc* d, const float* in1, const flo
     if (d->phase_sum == 1 || d->phase_sum == 2) {
         if (!w.split || w.kind != K2S1 || (d->phase_sum == 1 && d->gather1 != RCF_GATHER_STRIDED2)) return RCF_EUNSUPPORTED;
         nslot4 = wgrad_phase_slots(w.nsplit, d);
-        a.phase_sum = d->phase_sum;
         w.nsplit = (wgrad_phase_pairs(d) ? 2 : 4) * nslot4;   // workgroups: (slot, a) pairs / (slot, phase)
     }
-    a.vt = w.vt; a.hp = d->h_out + 1; a.nimg = d->n; a.inv_hp = 1.0f / (float)(d->h_out + 1);
-    a.sy = (float)d->h_src1 / (float)d->h_in;
-    a.sx = (float)d->w_src1 / (float)d->w_in;
-    a.tiles_x = w.tiles_x; a.tiles_y = w.tiles_y; a.ntiles = w.ntiles;
-    a.nchunk1 = w.nchunk1; a.nchunk2 = w.nchunk2;
-    a.in1 = in1; a.in2 = in2; a.wp = nullptr; a.out = nullptr; a.stats = nullptr; a.dz = dz; a.ws = workspace;
-    a.ktot = w.ktot; a.cop = w.cop;
-    hipStream_t st = (hipStream_t)stream;
-    const int nchunk = w.nchunk1 + w.nchunk2;
-    const int p16 = w.px == 16;
-    const bool dma = !SAct::B16 && w.kind != K7S2 && (d->c1 % 4 == 0) && (d->c2 % 4 == 0);
     if (w.split) {
         if (w.kind == K1 && d->stride == 2) {   // x at the even positions of the physical h_in x w_in tensor; logical input = output grid
             a.h_in = d->h_out; a.w_in = d->w_out; a.h1 = d->h_in; a.w1 = d->w_in;
@@ -3709,74 +3596,15 @@ static int conv2d_wgrad_impl(const rcf_conv_desc* d, const float* in1, const flo
         }
         a.nchunk1 = ceil_div(d->c1, 32 * w.wci);
         a.nchunk2 = d->c2 > 0 ? ceil_div(d->c2, 32 * w.wci) : 0;
-        const int cfg = w.wci * 10 + w.wco;
-        if (wgrad_tr_ok(d, w) && !coef1 && !coef2) {
-#ifdef RCF_WGRAD_DIAG
-            { const char* dg = getenv("RCF_WGRAD_DIAG"); if (dg && dg[0] >= '1' && dg[0] <= '3') a.xcd_band = 76 + (dg[0] - '0'); }
-#endif
-            constexpr int NPT = SAct::B16 ? 1 : 2;       // operand planes
-            constexpr int THT = SAct::B16 ? 16 : 8;      // tile rows of the 64-channel configurations (select_wgrad: th_split)
-            const int ks = w.kind == K3S1 ? 3 : (w.kind == K2S1 ? 2 : 1);
-#define RCF_TR_KS(KSV)                                                                                                  \
-            if (cfg == 22) rc = launch_wgrad_tr<WtCfg<2, 2, KSV, THT, NPT>>(a, w.nsplit, w.gy, w.gz, st);               \
-            else if (cfg == 12) rc = launch_wgrad_tr<WtCfg<1, 2, KSV, THT, NPT>>(a, w.nsplit, w.gy, w.gz, st);          \
-            else if (cfg == 21) rc = launch_wgrad_tr<WtCfg<2, 1, KSV, THT, NPT>>(a, w.nsplit, w.gy, w.gz, st);          \
-            else rc = launch_wgrad_tr<WtCfg<1, 1, KSV, 16, NPT>>(a, w.nsplit, w.gy, w.gz, st);
-            if (ks == 3) { RCF_TR_KS(3) }
-            else if (ks == 2) { RCF_TR_KS(2) }
-            else {
-                if constexpr (SAct::B16) { RCF_TR_KS(1) } else return RCF_EUNSUPPORTED;
-            }
-#undef RCF_TR_KS
-        } else
-        if (d->precision == RCF_PREC_BF16) {
-            constexpr int THB = SAct::B16 ? 16 : 8;   // tile rows (select_wgrad: th_split)
-            if (w.kind == K1) {
-                if constexpr (SAct::B16) {
-                    if (cfg == 22) rc = launch_wgrad_split<WsCfg<2, 2, 1, 16, 1>>(a, w.nsplit, w.gy, w.gz, st);
-                    else if (cfg == 12) rc = launch_wgrad_split<WsCfg<1, 2, 1, 16, 1>>(a, w.nsplit, w.gy, w.gz, st);
-                    else if (cfg == 21) rc = launch_wgrad_split<WsCfg<2, 1, 1, 16, 1>>(a, w.nsplit, w.gy, w.gz, st);
-                    else rc = launch_wgrad_split<WsCfg<1, 1, 1, 16, 1>>(a, w.nsplit, w.gy, w.gz, st);
-                } else return RCF_EUNSUPPORTED;
-            } else if (w.kind == K2S1 && a.phase_sum == 2) {
-                if (cfg == 22) rc = launch_wgrad_split<WsCfg<2, 2, 2, THB, 1, true>>(a, w.nsplit, w.gy, w.gz, st);
-                else if (cfg == 12) rc = launch_wgrad_split<WsCfg<1, 2, 2, THB, 1, true>>(a, w.nsplit, w.gy, w.gz, st);
-                else if (cfg == 21) rc = launch_wgrad_split<WsCfg<2, 1, 2, THB, 1, true>>(a, w.nsplit, w.gy, w.gz, st);
-                else rc = launch_wgrad_split<WsCfg<1, 1, 2, 16, 1, true>>(a, w.nsplit, w.gy, w.gz, st);
-            } else if (w.kind == K2S1) {
-                if (cfg == 22) rc = launch_wgrad_split<WsCfg<2, 2, 2, THB, 1>>(a, w.nsplit, w.gy, w.gz, st);
-                else if (cfg == 12) rc = launch_wgrad_split<WsCfg<1, 2, 2, THB, 1>>(a, w.nsplit, w.gy, w.gz, st);
-                else if (cfg == 21) rc = launch_wgrad_split<WsCfg<2, 1, 2, THB, 1>>(a, w.nsplit, w.gy, w.gz, st);
-                else rc = launch_wgrad_split<WsCfg<1, 1, 2, 16, 1>>(a, w.nsplit, w.gy, w.gz, st);
-            } else if (cfg == 22) rc = launch_wgrad_split<WsCfg<2, 2, 3, THB, 1>>(a, w.nsplit, w.gy, w.gz, st);
-            else if (cfg == 12) rc = launch_wgrad_split<WsCfg<1, 2, 3, THB, 1>>(a, w.nsplit, w.gy, w.gz, st);
-            else if (cfg == 21) rc = launch_wgrad_split<WsCfg<2, 1, 3, THB, 1>>(a, w.nsplit, w.gy, w.gz, st);
-            else rc = launch_wgrad_split<WsCfg<1, 1, 3, 16, 1>>(a, w.nsplit, w.gy, w.gz, st);
-        } else if constexpr (!SAct::B16) {
-            rc = d->precision == RCF_PREC_F16X2 ? launch_wgrad_split_planes<2>(a, w, cfg, st) : launch_wgrad_split_planes<3>(a, w, cfg, st);
-        } else return RCF_EUNSUPPORTED;
-    } else
-    switch (w.kind) {
-        case K3S1:
-            if (dma && w.px == 8) rc = RCF_DMA(launch_wgrad_dma<W3S1_8>(a, w.nsplit, nchunk, w.ncog, st));
-            else if (dma) rc = RCF_DMA(p16 ? launch_wgrad_dma<W3S1_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad_dma<W3S1_32>(a, w.nsplit, nchunk, w.ncog, st));
-            else rc = p16 ? launch_wgrad<W3S1_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad<W3S1_32>(a, w.nsplit, nchunk, w.ncog, st);
-            break;
-        case K3S2:
-            if (dma) rc = RCF_DMA(p16 ? launch_wgrad_dma<W3S2_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad_dma<W3S2_32>(a, w.nsplit, nchunk, w.ncog, st));
-            else rc = p16 ? launch_wgrad<W3S2_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad<W3S2_32>(a, w.nsplit, nchunk, w.ncog, st);
-            break;
-        case K1:
-            if (dma) rc = RCF_DMA(p16 ? launch_wgrad_dma<W1_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad_dma<W1_32>(a, w.nsplit, nchunk, w.ncog, st));
-            else rc = p16 ? launch_wgrad<W1_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad<W1_32>(a, w.nsplit, nchunk, w.ncog, st);
-            break;
-        case K2S1:
-            if (dma) rc = RCF_DMA(p16 ? launch_wgrad_dma<W2_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad_dma<W2_32>(a, w.nsplit, nchunk, w.ncog, st));
-            else rc = p16 ? launch_wgrad<W2_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad<W2_32>(a, w.nsplit, nchunk, w.ncog, st);
-            break;
-        case K7S2: rc = p16 ? launch_wgrad<W7_16>(a, w.nsplit, nchunk, w.ncog, st) : launch_wgrad<W7_32>(a, w.nsplit, nchunk, w.ncog, st); break;
-        default: return RCF_EUNSUPPORTED;
     }
+    hipStream_t st = (hipStream_t)stream;
+    rc = with_wgrad_cfg(d, w, bn, [&](auto fam, auto c) {
+        using Fam = decltype(fam);
+#ifdef RCF_WGRAD_DIAG
+        { const char* dg = getenv("RCF_WGRAD_DIAG"); if (Fam::TR && dg && dg[0] >= '1' && dg[0] <= '3') a.xcd_band = 76 + (dg[0] - '0'); }
+#endif
+        return Fam::template run<decltype(c)>(a, w, st);
+    });
     if (rc != RCF_OK) return rc;
     const int total = w.ktot * w.cop;
     const int ksx = w.kind == K7S2 ? 1 : d->ksize;

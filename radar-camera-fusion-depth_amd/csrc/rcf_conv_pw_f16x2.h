@@ -179,22 +179,4 @@ inline int pw2_grid(long long npix, int kst, int nt) {
     return (int)g;
 }
 
-template <class C>
-int launch_pw2(const ConvArgs& a, hipStream_t st) {
-    const int g = pw2_grid((long long)a.n * a.h_out * a.w_out, C::KST, C::NT);
-    hipLaunchKernelGGL((conv1x1_f16x2_kernel<C>), dim3(g), dim3(256), 0, st, a);
-    return rcf_launch_status();
-}
-
 inline bool pw2_cfg_ok(int kst, int nt) { return kst >= 1 && kst <= 4 && nt >= 1 && nt <= 4 && kst * nt <= 8; }
-
-template <class F>
-int dispatch_pw2(int kst, int nt, F&& f) {
-#define RCF_PW2(K, N) if (kst == K && nt == N) return f(Pw2Cfg<K, N>{})
-    RCF_PW2(1, 1); RCF_PW2(1, 2); RCF_PW2(1, 3); RCF_PW2(1, 4);
-    RCF_PW2(2, 1); RCF_PW2(2, 2); RCF_PW2(2, 3); RCF_PW2(2, 4);
-    RCF_PW2(3, 1); RCF_PW2(3, 2);
-    RCF_PW2(4, 1); RCF_PW2(4, 2);
-#undef RCF_PW2
-    return RCF_EUNSUPPORTED;
-}
