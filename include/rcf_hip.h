@@ -136,6 +136,27 @@ int rcf_device_ok(void);
 
 int rcf_conv2d_query(const rcf_conv_desc* d, rcf_conv_info* info);
 
+/* Diagnostics: the configuration-table entry a launch on `d` runs, decided by the same selection and table lookup as the launch.
+ * role RCF_ROLE_FWD: the forward form (rcf_conv2d_fwd / _bn / _scaled / _act / rcf_conv2d_dgrad_bn_sums, any w_mode);
+ * RCF_ROLE_WGRAD: rcf_conv2d_wgrad on the same forward descriptor.  RCF_EUNSUPPORTED where that launch has no kernel. */
+#define RCF_ROLE_FWD 0
+#define RCF_ROLE_WGRAD 1
+#define RCF_FAM_FWD 0   /* conv_fwd_kernel (f32 MFMA) */
+#define RCF_FAM_SPLIT 1 /* conv_split_kernel (one to three 16-bit operand planes) */
+#define RCF_FAM_DMA 2   /* conv_b16_kernel (bf16 tensors, LDS by DMA) */
+#define RCF_FAM_PW 3    /* the pointwise 1x1 kernels */
+#define RCF_FAM_WG 4    /* conv_wgrad_kernel / conv_wgrad_dma_kernel */
+#define RCF_FAM_WS 5    /* conv_wgrad_split_kernel */
+#define RCF_FAM_WT 6    /* conv_wgrad_tr_kernel */
+typedef struct rcf_conv_config {
+    int family;  /* RCF_FAM_* */
+    int index;   /* position of the entry in its family's list (of the translation unit of d->storage) */
+    int count;   /* length of that list */
+    int has_epi; /* the entry has the inference-epilogue variant (rcf_conv2d_fwd_act) */
+    int has_bst; /* the entry has the BatchNorm-backward-sums variant (rcf_conv2d_dgrad_bn_sums) */
+} rcf_conv_config;
+int rcf_conv2d_config(const rcf_conv_desc* d, int role, rcf_conv_config* out);
+
 /* OIHW -> kernel layout [n-tile][k-chunk][tap][BN][CK].  Replaces nothing in the reference; it is the
  * price of keeping torch.nn.Conv2d.weight's layout at the boundary. */
 int rcf_conv2d_pack_weights(const rcf_conv_desc* d, const float* w_oihw, float* packed, void* stream);

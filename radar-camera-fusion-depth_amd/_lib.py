@@ -30,6 +30,14 @@ class ConvInfo(Structure):
                 ('bn_on_load', c_int), ('wgrad_bn_on_load', c_int), ('fwd_act', c_int), ('bn_bwd_sums', c_int)]
 
 
+class ConvConfig(Structure):   # rcf_conv_config (rcf_conv2d_config: diagnostics)
+    _fields_ = [(n, c_int) for n in ('family', 'index', 'count', 'has_epi', 'has_bst')]
+
+
+RCF_ROLE_FWD, RCF_ROLE_WGRAD = 0, 1
+RCF_FAM_FWD, RCF_FAM_SPLIT, RCF_FAM_DMA, RCF_FAM_PW, RCF_FAM_WG, RCF_FAM_WS, RCF_FAM_WT = range(7)
+
+
 class PackItem(Structure):     # rcf_pack_item
     _fields_ = [('desc', POINTER(ConvDesc)), ('w_oihw', c_void_p), ('packed', c_void_p), ('amax_w', c_void_p)]
 
@@ -54,6 +62,7 @@ _SIGNATURES = {
     'rcf_version': (c_char_p, []),
     'rcf_device_ok': (c_int, []),
     'rcf_conv2d_query': (c_int, [POINTER(ConvDesc), POINTER(ConvInfo)]),
+    'rcf_conv2d_config': (c_int, [POINTER(ConvDesc), c_int, POINTER(ConvConfig)]),
     'rcf_conv2d_pack_weights': (c_int, [POINTER(ConvDesc), _P, _P, _P]),
     'rcf_conv2d_pack_weights_batch': (c_int, [POINTER(PackItem), c_int, _P]),
     'rcf_phase_weights_batch': (c_int, [POINTER(PhaseItem), c_int, _P]),

@@ -435,6 +435,11 @@ __global__ void __launch_bounds__(256, 2) conv_b16_kernel(ConvArgs a) {
             const unsigned pstep = 2u * pixb;                                   // bytes between the pixel pairs of neighbouring x
             unsigned char* outb = reinterpret_cast<unsigned char*>(a.out);
             const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(outb + (size_t)fim * img_b, 0, 0x7fffffff, 0x00020000);
+            // the inference epilogue's residual: lrelu(lrelu(conv + bias) + res), res laid out like out
+            const bool has_res = EPI && a.res != nullptr;
+            const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(has_res ? a.res : a.out)) + (size_t)fim * img_b, 0,
+                0x7fffffff, 0x00020000);
             const int wlim = a.w_out - ox0;   // (the physical width is 2 w_out: valid_desc)
             const unsigned xoff = (unsigned)(2 * ox0) * pixb + (unsigned)n0 * 2u;
             // per lane: byte offset of its dword inside a row block (column 4 lh of x, pixel 2x + odd, channel pair li & ~1)
@@ -485,6 +490,11 @@ __global__ void __launch_bounds__(256, 2) conv_b16_kernel(ConvArgs a) {
                                     if constexpr (EPI) {
                                         lo = rcf_lrelu(lo + eb[ni][0]);
                                         hi = rcf_lrelu(hi + eb[ni][1]);
+                                        if (has_res) {
+                                            const unsigned rw = __builtin_amdgcn_raw_buffer_load_b32(rs_res, vo, so, 0);
+                                            lo = rcf_lrelu(lo + __uint_as_float(rw << 16));
+                                            hi = rcf_lrelu(hi + __uint_as_float(rw & 0xffff0000u));
+                                        }
                                     }
                                     const unsigned pk = rcf_f2b2(lo, hi);
                                     __builtin_amdgcn_raw_buffer_store_b32(pk, rs_out, vo, so, 0);
@@ -947,7 +957,8 @@ __global__ void __launch_bounds__(256, 2) conv1x1_b16_kernel(ConvArgs a) {
 // output channels one workgroup of the pointwise kernel takes (in 32-channel tiles) and the pixel blocks per trip
 inline int pw_nt(int kst, int nt_total) {
     if (kst >= 16) return 1;
-    if (kst >= 8 || (kst == 4 && nt_total == 4)) return nt_total < 2 ? nt_total : 2;   // (64 -> 128 in one workgroup spilled 34 VGPRs)
+    // (64 -> 128 in one workgroup spilled 34 VGPRs; 48 -> 65..128 takes two workgroups like it: PwList has no (3, 3) / (3, 4))
+    if (kst >= 8 || (kst == 4 && nt_total == 4) || kst == 3) return nt_total < 2 ? nt_total : 2;
     return nt_total;
 }
 inline int pw_mt(int kst, int nt) { return kst >= 8 ? 1 : (nt <= 2 ? 4 : 1); }

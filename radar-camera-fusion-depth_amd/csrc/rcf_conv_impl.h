@@ -2853,6 +2853,8 @@ int select_wgrad(const rcf_conv_desc* d, WSel* w) {
         w->kind = d->stride == 2 ? K3S2 : K3S1; w->t = 9; w->cst = 32;
     } else {
         w->kind = K1; w->t = 1; w->cst = 32;
+        // bf16 tensors: the split kernel's stride-2 projection re-addresses source 1 only (conv2d_wgrad_impl), so no second source
+        if (SAct::B16 && d->stride == 2 && d->c2 != 0) return RCF_EUNSUPPORTED;
     }
     if ((d->c1 % 4 != 0 || d->c2 % 4 != 0) && w->kind != K7S2 && d->c2 != 0) return RCF_EUNSUPPORTED;
     const int th32 = (w->kind == K3S2) ? 4 : 8;
@@ -3002,6 +3004,7 @@ struct FwdFam : Tiles<FwdFam> {   // conv_fwd_kernel: the f32 MFMA
     template <class C, bool E, bool B> static constexpr auto kernel = &conv_fwd_kernel<C>;
     static constexpr bool HAS_EPI = false;
     template <class C> static constexpr bool has_bst = false;
+    template <class C> static constexpr bool has_stats = true;
 };
 
 struct SplitFam : Tiles<SplitFam> {   // conv_split_kernel: fp32 arithmetic on the 16-bit matrix pipe, one to three operand planes
@@ -3010,6 +3013,7 @@ struct SplitFam : Tiles<SplitFam> {   // conv_split_kernel: fp32 arithmetic on t
     static constexpr bool HAS_EPI = true;
     // the BatchNorm-backward sums: fp32 tensors on two fp16 planes, 3x3 stride 1 and 2x2, one output phase
     template <class C> static constexpr bool has_bst = C::NPL == 2 && C::LSTEP == 1 && !C::P4 && (C::KSY == 3 || C::KSY == 2);
+    template <class C> static constexpr bool has_stats = true;
 };
 
 #if RCF_CONV_B16
@@ -3020,6 +3024,8 @@ struct DmaFam : Tiles<DmaFam> {   // conv_b16_kernel (rcf_conv_b16_dma.h): bf16 
     // the BatchNorm-backward sums: every 3x3 stride-1 and 2x2 configuration (round 5: the buffer-addressed epilogue freed ~40
     // registers; the 64-co x 32-pixel-row one had been excluded for its spills)
     template <class C> static constexpr bool has_bst = C::LSTEP == 1 && !C::P4 && (C::KS == 3 || C::KS == 2);
+    // BatchNorm statistics: not of the merged stride-2 input gradient (an input gradient takes none; refused, not left zero)
+    template <class C> static constexpr bool has_stats = C::PM != 2;
 };
 
 // grid of the pointwise kernel: x = the BatchNorm partial rows it writes, y walks the output channels 32 * nt at a time
@@ -3049,6 +3055,7 @@ struct PwFam {
 #endif
     static constexpr bool HAS_EPI = false;
     template <class C> static constexpr bool has_bst = false;
+    template <class C> static constexpr bool has_stats = true;
     template <class C> static int grid_x(const ConvArgs& a, int) { return pw_dims(a, C::KST, C::NT).x; }
     template <class C, bool E, bool B>
     static int run(const ConvArgs& a, int, hipStream_t st) { return launch<kernel<C>>(pw_dims(a, C::KST, C::NT), dim3(256), 0, st, a); }
@@ -3202,6 +3209,27 @@ using WsList = Cat<WsQuad<3, 1>, WsQuad<2, 1>, WsQuad<2, 1, true>, WsQuad<3, 2>,
 using WtList = Cat<WtQuad<3, 2>, WtQuad<2, 2>>::type;
 #endif
 
+// rcf_conv2d_config: a family's list, its RCF_FAM_* number and a configuration's position in it
+template <class Fam> struct ListOf;
+template <> struct ListOf<FwdFam> { using type = FwdList; static constexpr int FAMILY = RCF_FAM_FWD; };
+template <> struct ListOf<SplitFam> { using type = SplitList; static constexpr int FAMILY = RCF_FAM_SPLIT; };
+#if RCF_CONV_B16
+template <> struct ListOf<DmaFam> { using type = DmaList; static constexpr int FAMILY = RCF_FAM_DMA; };
+#endif
+template <> struct ListOf<PwFam> { using type = PwList; static constexpr int FAMILY = RCF_FAM_PW; };
+template <> struct ListOf<WgFam> { using type = WgList; static constexpr int FAMILY = RCF_FAM_WG; };
+template <> struct ListOf<WsFam> { using type = WsList; static constexpr int FAMILY = RCF_FAM_WS; };
+template <> struct ListOf<WtFam> { using type = WtList; static constexpr int FAMILY = RCF_FAM_WT; };
+
+template <class T, class Fam, class... C>
+constexpr int index_in(List<Fam, C...>) {
+    int i = 0, r = -1;
+    (void)((std::is_same<T, C>::value ? (r = i, true) : (++i, false)) || ...);
+    return r;
+}
+template <class Fam, class... C>
+constexpr int list_size(List<Fam, C...>) { return (int)sizeof...(C); }
+
 // operand planes of a split weight gradient: 1 (RCF_PREC_BF16), 2 (RCF_PREC_F16X2), 3 (exact)
 int wgrad_planes(const rcf_conv_desc* d) { return d->precision == RCF_PREC_BF16 ? 1 : (d->precision == RCF_PREC_F16X2 ? 2 : 3); }
 
@@ -3249,6 +3277,7 @@ size_t packed_floats(const rcf_conv_desc* d, const Sel& s) {
     if ((d) != nullptr && (d)->storage == RCF_STORE_BF16) return call
 extern "C" {
 int rcf_conv2d_query_b16impl(const rcf_conv_desc* d, rcf_conv_info* info);
+int rcf_conv2d_config_b16impl(const rcf_conv_desc* d, int role, rcf_conv_config* out);
 int rcf_conv2d_dgrad_bn_sums_b16impl(const rcf_conv_desc* d, const void* dz, const float* packed, void* dx, const void* bn_z,
                                      const float* bn_coef, double* sum_partials, const rcf_conv_scales* scales, void* stream);
 int rcf_conv2d_pack_weights_b16impl(const rcf_conv_desc* d, const float* w_oihw, float* packed, void* stream);
@@ -3324,21 +3353,15 @@ extern "C" int RCF_FN(rcf_conv2d_query)(const rcf_conv_desc* d, rcf_conv_info* i
     ConvArgs a;
     fill_args(d, s, &a);
     info->packed_weight_floats = packed_floats(d, s);
-    info->fwd_act = 0;
-    info->bn_bwd_sums = 0;
-    if (s.pw) {   // (from the selection: PwCfg has no (3, 3) / (3, 4) entry, and the launch of those answers RCF_EUNSUPPORTED)
-        info->n_partials = pw_dims(a, d->c1 / 16, s.nt).x;
-    } else {
-        rc = with_fwd_cfg(d, s, [&](auto fam, auto c) {
-            using Fam = decltype(fam);
-            using C = decltype(c);
-            info->n_partials = Fam::template grid_x<C>(a, ceil_div(d->c_out, s.bn));
-            info->fwd_act = (Fam::HAS_EPI && fwd_act_ok(d)) ? 1 : 0;
-            info->bn_bwd_sums = (Fam::template has_bst<C> && bn_sums_ok(d)) ? 1 : 0;
-            return RCF_OK;
-        });
-        if (rc != RCF_OK) return rc;
-    }
+    rc = with_fwd_cfg(d, s, [&](auto fam, auto c) {
+        using Fam = decltype(fam);
+        using C = decltype(c);
+        info->n_partials = Fam::template grid_x<C>(a, ceil_div(d->c_out, s.bn));
+        info->fwd_act = (Fam::HAS_EPI && fwd_act_ok(d)) ? 1 : 0;
+        info->bn_bwd_sums = (Fam::template has_bst<C> && bn_sums_ok(d)) ? 1 : 0;
+        return RCF_OK;
+    });
+    if (rc != RCF_OK) return rc;
     info->kernel_id = kernel_id(s);
     info->wgrad_workspace_floats = 0;
     info->wgrad_kernel_id = 0;
@@ -3357,6 +3380,34 @@ extern "C" int RCF_FN(rcf_conv2d_query)(const rcf_conv_desc* d, rcf_conv_info* i
         }
     }
     return RCF_OK;
+}
+
+// the table entry the launch of `role` on d runs: found by with_fwd_cfg / with_wgrad_cfg (no BatchNorm-on-load) like the launches
+extern "C" int RCF_FN(rcf_conv2d_config)(const rcf_conv_desc* d, int role, rcf_conv_config* out) {
+    RCF_TO_B16(d, rcf_conv2d_config_b16impl(d, role, out));
+    if (!d || !out || (role != RCF_ROLE_FWD && role != RCF_ROLE_WGRAD)) return RCF_EINVAL;
+    auto put = [out](auto fam, auto c, bool epi, bool bst) {
+        using L = typename ListOf<decltype(fam)>::type;
+        out->family = ListOf<decltype(fam)>::FAMILY;
+        out->index = index_in<decltype(c)>(L{});
+        out->count = list_size(L{});
+        out->has_epi = epi ? 1 : 0;
+        out->has_bst = bst ? 1 : 0;
+        return RCF_OK;
+    };
+    if (role == RCF_ROLE_FWD) {
+        Sel s;
+        const int rc = select_cfg(d, &s);
+        if (rc != RCF_OK) return rc;
+        return with_fwd_cfg(d, s, [&](auto fam, auto c) {
+            using Fam = decltype(fam);
+            return put(fam, c, Fam::HAS_EPI, Fam::template has_bst<decltype(c)>);
+        });
+    }
+    WSel w;
+    const int rc = select_wgrad(d, &w);
+    if (rc != RCF_OK) return rc;
+    return with_wgrad_cfg(d, w, false, [&](auto fam, auto c) { return put(fam, c, false, false); });
 }
 
 // arguments of one weight packing (shared by the single and the batched entry point)
@@ -3532,6 +3583,7 @@ static int conv2d_fwd_impl(const rcf_conv_desc* d, const float* in1, const float
                 if (bn_sums_ok(d)) return Fam::template run<C, false, true>(a, nn, (hipStream_t)stream);
             return RCF_EUNSUPPORTED;
         }
+        if (a.stats != nullptr && !Fam::template has_stats<C>) return RCF_EUNSUPPORTED;
         return Fam::template run<C, false, false>(a, nn, (hipStream_t)stream);
     });
 }

@@ -333,6 +333,13 @@ def conv_query(desc):
     return info
 
 
+def conv_config(desc, role=_lib.RCF_ROLE_FWD):
+    """The configuration-table entry (_lib.ConvConfig: family, index, count, has_epi, has_bst) the launch of `role` on desc runs."""
+    cfg = _lib.ConvConfig()
+    check(_lib.load().rcf_conv2d_config(ctypes.byref(desc), role, ctypes.byref(cfg)), 'rcf_conv2d_config')
+    return cfg
+
+
 def conv_pack(desc, w_oihw, packed, amax_w=None):
     """amax_w (RCF_PREC_F16X2 descriptors): device scalar holding max|w| -- the fp16 planes hold w * its power-of-two scale."""
     if amax_w is not None:

@@ -50,7 +50,8 @@ CONV_CASES = [
     (3, 1, 16, 0, 32, 2, 20, 37, None),
     (3, 1, 64, 0, 64, 1, 33, 64, None),
     (3, 1, 64, 32, 64, 2, 17, 40, None),        # decoder concat 64+32 -> 64 (deconv1.conv)
-    (3, 1, 32, 0, 32, 1, 40, 100, None),        # w=100 picks the 16x16 tile
+    (3, 1, 32, 0, 32, 1, 40, 100, None),        # 32-co layer: 512-pixel tiles of 32-pixel rows (w = 100 wastes less on 4 x 32)
+    (3, 1, 32, 0, 32, 1, 30, 48, None),         # w = 48: 512-pixel tiles of 16-pixel rows
     (3, 1, 8, 8, 8, 2, 35, 51, None),           # tiny net concat, CK=8 path
     (3, 1, 4, 0, 4, 2, 70, 102, None),          # tiny net deconv0
     (3, 1, 256, 0, 128, 1, 29, 50, (15, 25)),   # UpConv 15x25 -> 29x50 (non-2x nearest)
