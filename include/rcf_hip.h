@@ -286,6 +286,35 @@ int rcf_fuse_fwd(const float* zw, const float* coef_w, const float* zp, const fl
 int rcf_fuse_fwd_amax(const float* zw, const float* coef_w, const float* zp, const float* coef_p,
                       const float* img, float* out, long long n_pix, int c, float* amax, void* stream);
 
+/* skip = BN(z) + img : FusionNetEncoder 'add' fusion (src/networks.py:857-859; z = conv_project's raw output, no activation,
+ * :351-358).  Its backward is rcf_bn_act_bwd_reduce / _apply on dout with RCF_ACT_NONE and has_res = 0, plus dimg (+)= dout. */
+int rcf_fuse_add_fwd(const float* z, const float* coef, const float* img, float* out, long long n_pix, int c, void* stream);
+int rcf_fuse_add_fwd_amax(const float* z, const float* coef, const float* img, float* out, long long n_pix, int c, float* amax,
+                          void* stream);
+
+/* skip = sigmoid(BN_w(zw)) * d + img : FusionNetEncoder 'weight' fusion (src/networks.py:860-862; zw = conv_weight's raw output, a
+ * 3x3 convolution of the depth activation d with as many output channels, :362-369 -- so d, img and out share one width c).
+ * bwd_reduce: partials[n_blocks][2][c] = (sum gw, sum gw*xhat_w), gw = dout * d * sig * (1 - sig); feed rcf_bn_bwd_finalize.
+ * bwd_apply: dzw = scale_w * (gw - b0 - xhat_w * b1), dd (+)= dout * sig, dimg (+)= dout; dd / dimg may be null (skipped). */
+int rcf_fuse_weight_fwd(const float* zw, const float* coef_w, const float* d, const float* img, float* out, long long n_pix, int c,
+                        void* stream);
+int rcf_fuse_weight_fwd_amax(const float* zw, const float* coef_w, const float* d, const float* img, float* out, long long n_pix, int c,
+                             float* amax, void* stream);
+int rcf_fuse_weight_bwd_reduce(const float* dout, const float* zw, const float* coef_w, const float* d, double* partials,
+                               long long n_pix, int c, void* stream);
+int rcf_fuse_weight_bwd_apply(const float* dout, const float* zw, const float* coef_w, const float* d, const float* bcoef_w, float* dzw,
+                              float* dd, int dd_accumulate, float* dimg, int dimg_accumulate, long long n_pix, int c, void* stream);
+
+/* FusionNetEncoder 'concat' fusion: torch.cat([a, b], dim=1) in NHWC, out[p] = [a[p] | b[p]] (src/networks.py:892: [image | depth];
+ * :868, level 1 only: [depth | image] -- the caller orders a and b).  a [n_pix][ca], b [n_pix][cb], out [n_pix][ca + cb]; ca and cb
+ * multiples of 4 (the published pairs give 48, 96, 192, 384: no power of two is needed), else RCF_EUNSUPPORTED.  amax_out (optional, device, zeroed by the caller; then
+ * amax_a / amax_b are required): receives max(*amax_a, *amax_b), the maximum of the interleaved tensor at no pass over it.
+ * bwd: da (+)= dout[:, :ca], db (+)= dout[:, ca:]; a null da or db is skipped (at least one must be given). */
+int rcf_concat_fwd(const float* a, const float* b, float* out, long long n_pix, int ca, int cb, const float* amax_a,
+                   const float* amax_b, float* amax_out, void* stream);
+int rcf_concat_bwd(const float* dout, float* da, int da_accumulate, float* db, int db_accumulate, long long n_pix, int ca, int cb,
+                   void* stream);
+
 /* Backward of rcf_bn_act_fwd, two passes around a per-channel reduction (BatchNorm2d backward).
  * reduce: partials[n_blocks][2][c] (fp64: these sums cancel heavily, and PyTorch's CPU BatchNorm accumulates float
  * tensors in double) = (sum g, sum g*xhat), g = dout * act'(.) (* lrelu'(out) when has_res).
@@ -511,6 +540,8 @@ int rcf_points_to_depth_map(const float* xs, const float* ys, const float* depth
  * workspaces, the radar points and the fully connected activations -- keeps the type written in the fp32 declaration.  Arithmetic
  * is fp32 on the loaded values.  The convolutions take the storage in rcf_conv_desc.storage instead of a twin.
  * Which arguments are bf16 in the twin:
+ *   rcf_fuse_weight_fwd_b16 zw, d, img, out | rcf_fuse_weight_bwd_reduce_b16 dout, zw, d | rcf_fuse_weight_bwd_apply_b16 dout, zw,
+ *   d, dzw, dd, dimg | rcf_fuse_add_fwd_b16 z, img, out | rcf_concat_fwd_b16 a, b, out | rcf_concat_bwd_b16 dout, da, db |
  *   rcf_bn_act_fwd_b16 z, res, out | rcf_fuse_fwd_b16 zw, zp, img, out | rcf_bn_act_bwd_reduce_b16 dout, z, out |
  *   rcf_bn_act_bwd_apply_b16 dout, z, out, dz, dres | rcf_fuse_bwd_reduce_b16 dout, zw, zp | rcf_fuse_bwd_apply_b16 dout, zw, zp,
  *   dzw, dzp, dimg | rcf_head_bn_bwd_reduce_b16 z | rcf_head_bn_bwd_apply_b16 z, dz | rcf_maxpool3x3s2_fwd_b16 in, out |
@@ -522,6 +553,18 @@ int rcf_points_to_depth_map(const float* xs, const float* ys, const float* depth
 int rcf_bn_act_fwd_b16(const float* z, const float* coef, const float* res, float* out, long long n_pix, int c, int act, void* stream);
 int rcf_fuse_fwd_b16(const float* zw, const float* coef_w, const float* zp, const float* coef_p, const float* img, float* out,
                      long long n_pix, int c, void* stream);
+int rcf_fuse_add_fwd_b16(const float* z, const float* coef, const float* img, float* out, long long n_pix, int c, void* stream);
+int rcf_fuse_weight_fwd_b16(const float* zw, const float* coef_w, const float* d, const float* img, float* out, long long n_pix, int c,
+                            void* stream);
+int rcf_fuse_weight_bwd_reduce_b16(const float* dout, const float* zw, const float* coef_w, const float* d, double* partials,
+                                   long long n_pix, int c, void* stream);
+int rcf_fuse_weight_bwd_apply_b16(const float* dout, const float* zw, const float* coef_w, const float* d, const float* bcoef_w,
+                                  float* dzw, float* dd, int dd_accumulate, float* dimg, int dimg_accumulate, long long n_pix, int c,
+                                  void* stream);
+int rcf_concat_fwd_b16(const float* a, const float* b, float* out, long long n_pix, int ca, int cb, const float* amax_a,
+                       const float* amax_b, float* amax_out, void* stream);
+int rcf_concat_bwd_b16(const float* dout, float* da, int da_accumulate, float* db, int db_accumulate, long long n_pix, int ca, int cb,
+                       void* stream);
 int rcf_bn_act_bwd_reduce_b16(const float* dout, const float* z, const float* coef, const float* out, double* partials, long long n_pix,
                               int c, int act, int has_res, void* stream);
 int rcf_bn_act_bwd_apply_b16(const float* dout, const float* z, const float* coef, const float* out, const float* bcoef, float* dz,
@@ -534,6 +577,11 @@ int rcf_bn_act_bwd_apply_b16(const float* dout, const float* z, const float* coe
 int rcf_fuse_wp_infer_supported(int c_d, int c_i);
 int rcf_fuse_wp_infer_b16(const float* d, const float* w1, const float* coef_w, const float* w2, const float* coef_p, const float* img,
                           float* out, long long n_pix, int c_d, int c_i, void* stream);
+/* Inference form of the 'add' fusion (src/networks.py:857-859 with the BatchNorm in eval mode) on bf16 tensors, one pass:
+ * out = scale * (W d) + shift + img.  The sibling of rcf_fuse_wp_infer_b16: same layouts, same supported widths
+ * (rcf_fuse_wp_infer_supported(c_d, c_i)), RCF_EUNSUPPORTED otherwise.  Replaces rcf_conv2d_fwd + rcf_fuse_add_fwd_b16. */
+int rcf_fuse_add_infer_b16(const float* d, const float* w, const float* coef, const float* img, float* out, long long n_pix, int c_d,
+                           int c_i, void* stream);
 int rcf_fuse_bwd_reduce_b16(const float* dout, const float* zw, const float* coef_w, const float* zp, const float* coef_p,
                             double* partials, long long n_pix, int c, void* stream);
 int rcf_fuse_bwd_apply_b16(const float* dout, const float* zw, const float* coef_w, const float* zp, const float* coef_p,

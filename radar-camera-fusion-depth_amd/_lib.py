@@ -78,6 +78,12 @@ _SIGNATURES = {
     'rcf_bn_finalize': (c_int, [_P, c_int, c_int, c_double, _P, _P, _P, _P, c_float, c_float, c_int, _P, _P]),
     'rcf_bn_act_fwd': (c_int, [_P, _P, _P, _P, c_longlong, c_int, c_int, _P]),
     'rcf_fuse_fwd': (c_int, [_P, _P, _P, _P, _P, _P, c_longlong, c_int, _P]),
+    'rcf_fuse_add_fwd': (c_int, [_P, _P, _P, _P, c_longlong, c_int, _P]),
+    'rcf_fuse_weight_fwd': (c_int, [_P, _P, _P, _P, _P, c_longlong, c_int, _P]),
+    'rcf_fuse_weight_bwd_reduce': (c_int, [_P, _P, _P, _P, _P, c_longlong, c_int, _P]),
+    'rcf_fuse_weight_bwd_apply': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_longlong, c_int, _P]),
+    'rcf_concat_fwd': (c_int, [_P, _P, _P, c_longlong, c_int, c_int, _P, _P, _P, _P]),
+    'rcf_concat_bwd': (c_int, [_P, _P, c_int, _P, c_int, c_longlong, c_int, c_int, _P]),
     'rcf_ew_blocks': (c_int, [c_longlong, c_int]),
     'rcf_bn_act_bwd_reduce': (c_int, [_P, _P, _P, _P, _P, c_longlong, c_int, c_int, c_int, _P]),
     'rcf_bn_bwd_finalize': (c_int, [_P, c_int, c_int, c_int, c_double, _P, _P, _P, _P]),
@@ -130,7 +136,8 @@ _SIGNATURES = {
     'rcf_radar_scatter': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     'rcf_radar_scatter_logits': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
 }
-B16_TWINS = ('rcf_bn_act_fwd', 'rcf_fuse_fwd', 'rcf_bn_act_bwd_reduce', 'rcf_bn_act_bwd_apply', 'rcf_fuse_bwd_reduce', 'rcf_fuse_bwd_apply',
+B16_TWINS = ('rcf_bn_act_fwd', 'rcf_fuse_fwd', 'rcf_fuse_add_fwd', 'rcf_concat_fwd', 'rcf_concat_bwd',
+             'rcf_fuse_weight_fwd', 'rcf_fuse_weight_bwd_reduce', 'rcf_fuse_weight_bwd_apply', 'rcf_bn_act_bwd_reduce', 'rcf_bn_act_bwd_apply', 'rcf_fuse_bwd_reduce', 'rcf_fuse_bwd_apply',
              'rcf_head_bn_bwd_reduce', 'rcf_head_bn_bwd_apply', 'rcf_maxpool3x3s2_fwd', 'rcf_maxpool3x3s2_bwd', 'rcf_upsample_nearest_bwd',
              'rcf_head_fwd', 'rcf_head_fwd_bn', 'rcf_head_bwd_dgrad', 'rcf_head_bwd_wgrad', 'rcf_head_bwd_wgrad_bn', 'rcf_roi_pool_fwd',
              'rcf_roi_pool_bwd', 'rcf_roi_pool_bwd_gather', 'rcf_fc_fwd', 'rcf_fc_bwd')
@@ -146,12 +153,15 @@ _SIGNATURES.update({
     'rcf_amax_batch': (c_int, [POINTER(AmaxItem), c_int, _P]),
     'rcf_bn_act_fwd_amax': (c_int, [_P, _P, _P, _P, c_longlong, c_int, c_int, _P, _P]),
     'rcf_fuse_fwd_amax': (c_int, [_P, _P, _P, _P, _P, _P, c_longlong, c_int, _P, _P]),
+    'rcf_fuse_weight_fwd_amax': (c_int, [_P, _P, _P, _P, _P, c_longlong, c_int, _P, _P]),
+    'rcf_fuse_add_fwd_amax': (c_int, [_P, _P, _P, _P, c_longlong, c_int, _P, _P]),
     'rcf_bn_act_bwd_apply_amax': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_longlong, c_int, c_int, c_int, _P, _P]),
     'rcf_head_bn_bwd_apply_amax': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
 })
 _SIGNATURES['rcf_convert'] = (c_int, [_P, c_int, _P, c_int, c_longlong, c_int, _P])
 _SIGNATURES['rcf_fuse_wp_infer_supported'] = (c_int, [c_int, c_int])
 _SIGNATURES['rcf_fuse_wp_infer_b16'] = (c_int, [_P, _P, _P, _P, _P, _P, _P, c_longlong, c_int, c_int, _P])
+_SIGNATURES['rcf_fuse_add_infer_b16'] = (c_int, [_P, _P, _P, _P, _P, c_longlong, c_int, c_int, _P])
 _SIGNATURES['rcf_s2d_image_b16'] = (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P])
 _SIGNATURES['rcf_s2d_image_f32'] = (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P])
 _SIGNATURES['rcf_stem_weights_s2d'] = (c_int, [_P, _P, c_int, c_int, _P])

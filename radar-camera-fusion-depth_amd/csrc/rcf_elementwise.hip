@@ -1,5 +1,5 @@
-// BatchNorm2d (training + eval), LeakyReLU, the ResNet residual tail and the 'weight_and_project' fusion of
-// FusionNet, forward and backward, for NHWC fp32 tensors on gfx950.
+// BatchNorm2d (training + eval), LeakyReLU, the ResNet residual tail and the 'weight_and_project', 'add', 'weight' and
+// 'concat' fusions of FusionNet, forward and backward, for NHWC fp32 tensors on gfx950.
 //
 // Replaces, on the reference's hot path: torch.nn.BatchNorm2d + LeakyReLU inside net_utils.Conv2d.forward
 // (src/net_utils.py:84-91), the tail of ResNetBlock.forward (src/net_utils.py:309-323), the fusion at
@@ -142,6 +142,228 @@ __device__ __forceinline__ void block_reduce_store(const double (&s)[NS][4], dou
         for (int r = 0; r < ppb; ++r) t += sm[r * NS * c + e];
         partial_row[e] = t;
     }
+}
+
+// ---------------------------------------------------------------- 'add', 'weight' and 'concat' fusions (src/networks.py:857-862, :867-868)
+// out = BN(z) + img: the 'add' fusion (no activation on the projected depth features).  Its backward is a plain BatchNorm backward on
+// g = dout (bn_act_bwd_reduce / _apply with RCF_ACT_NONE) and dimg (+)= dout.
+template <class S, bool AM = false>
+__global__ void __launch_bounds__(256) fuse_add_fwd_kernel(const float* __restrict__ z, const float* __restrict__ coef,
+                                                           const float* __restrict__ img, float* __restrict__ out,
+                                                           long long n_pix, int c, float* __restrict__ amax = nullptr) {
+    float am = 0.f;
+    const int c4n = c >> 2;
+    const int cg = threadIdx.x % c4n;
+    const int pl = threadIdx.x / c4n;
+    const int ppb = 256 / c4n;
+    const Coef4 k = load_coef(coef, c, cg);
+    const long long stride = (long long)gridDim.x * ppb;
+    auto one = [&](f32x4 zz, f32x4 im, size_t i) {
+        const f32x4 y = zz * k.scale + k.shift + im;
+        st4<S>(out, i, y);
+        if (AM) am = rcf_amax4(am, y);
+    };
+    // one pixel per trip, like fuse_fwd_kernel: with two reads per write the EW_U-unrolled form (four distant pixels in flight per
+    // thread) measured 4.9 against 5.4 TB/s at the published batch-8 shapes (profiles/fusion_types_kernels.md)
+    for (long long p = (long long)blockIdx.x * ppb + pl; p < n_pix; p += stride) {
+        const size_t i = (size_t)p * c + cg * 4;
+        one(ld4<S>(z, i), ld4<S>(img, i), i);
+    }
+    if (AM) rcf_amax_commit(am, amax);
+}
+
+// out = sigmoid(BN(zw)) * d + img: the 'weight' fusion (src/networks.py:860-862; zw = conv_weight's raw output, a 3x3 convolution of d
+// with as many output channels, :362-369).
+template <class S, bool AM = false>
+__global__ void __launch_bounds__(256) fuse_weight_fwd_kernel(const float* __restrict__ zw, const float* __restrict__ coef_w,
+                                                              const float* __restrict__ d, const float* __restrict__ img,
+                                                              float* __restrict__ out, long long n_pix, int c,
+                                                              float* __restrict__ amax = nullptr) {
+    float am = 0.f;
+    const int c4n = c >> 2;
+    const int cg = threadIdx.x % c4n;
+    const int pl = threadIdx.x / c4n;
+    const int ppb = 256 / c4n;
+    const Coef4 kw = load_coef(coef_w, c, cg);
+    const long long stride = (long long)gridDim.x * ppb;
+    auto one = [&](f32x4 a, f32x4 dd, f32x4 im, size_t i) {
+        const f32x4 yw = a * kw.scale + kw.shift;
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (1.f / (1.f + expf(-yw[j]))) * dd[j] + im[j];
+        st4<S>(out, i, o);
+        if (AM) am = rcf_amax4(am, o);
+    };
+    long long p = (long long)blockIdx.x * ppb + pl;
+    for (; p + (EW_U - 1) * stride < n_pix; p += EW_U * stride) {
+        f32x4 a[EW_U], dd[EW_U], im[EW_U];
+#pragma unroll
+        for (int u = 0; u < EW_U; ++u) {
+            const size_t i = (size_t)(p + u * stride) * c + cg * 4;
+            a[u] = ld4<S>(zw, i);
+            dd[u] = ld4<S>(d, i);
+            im[u] = ld4<S>(img, i);
+        }
+#pragma unroll
+        for (int u = 0; u < EW_U; ++u) one(a[u], dd[u], im[u], (size_t)(p + u * stride) * c + cg * 4);
+    }
+    for (; p < n_pix; p += stride) {
+        const size_t i = (size_t)p * c + cg * 4;
+        one(ld4<S>(zw, i), ld4<S>(d, i), ld4<S>(img, i), i);
+    }
+    if (AM) rcf_amax_commit(am, amax);
+}
+
+// Backward of fuse_weight_fwd, pass 1: partials[blk][2][c] = (sum gw, sum gw * xhat_w), gw = dout * d * sig * (1 - sig).
+template <class S>
+__global__ void __launch_bounds__(256) fuse_weight_bwd_reduce_kernel(const float* __restrict__ dout, const float* __restrict__ zw,
+                                                                     const float* __restrict__ coef_w, const float* __restrict__ d,
+                                                                     double* __restrict__ partials, long long n_pix, int c) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int c4n = c >> 2;
+    const int cg = threadIdx.x % c4n;
+    const int pl = threadIdx.x / c4n;
+    const int ppb = 256 / c4n;
+    const Coef4 kw = load_coef(coef_w, c, cg);
+    double s[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    const long long stride = (long long)gridDim.x * ppb;
+    auto one = [&](f32x4 g, f32x4 a, f32x4 dd) {
+        const f32x4 yw = a * kw.scale + kw.shift;
+        const f32x4 xw = (a - kw.mean) * kw.invstd;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float sg = 1.f / (1.f + expf(-yw[j]));
+            const float gw = g[j] * dd[j] * sg * (1.f - sg);
+            s[0][j] += (double)gw;
+            s[1][j] += (double)gw * (double)xw[j];
+        }
+    };
+    long long p = (long long)blockIdx.x * ppb + pl;
+    for (; p + (EW_U - 1) * stride < n_pix; p += EW_U * stride) {   // same pixel order per thread as the one-at-a-time loop
+        f32x4 g[EW_U], a[EW_U], dd[EW_U];
+#pragma unroll
+        for (int u = 0; u < EW_U; ++u) {
+            const size_t i = (size_t)(p + u * stride) * c + cg * 4;
+            g[u] = ld4<S>(dout, i);
+            a[u] = ld4<S>(zw, i);
+            dd[u] = ld4<S>(d, i);
+        }
+#pragma unroll
+        for (int u = 0; u < EW_U; ++u) one(g[u], a[u], dd[u]);
+    }
+    for (; p < n_pix; p += stride) {
+        const size_t i = (size_t)p * c + cg * 4;
+        one(ld4<S>(dout, i), ld4<S>(zw, i), ld4<S>(d, i));
+    }
+    block_reduce_store<2>(s, partials + (size_t)blockIdx.x * 2 * c, c, cg, pl, sm);
+}
+
+// pass 2: dzw = scale_w * (gw - b0 - xhat_w * b1), dd (+)= dout * sig (the gate product's share of the depth activation's gradient; the
+// gate convolution's input gradient and the next block's are the other two), dimg (+)= dout
+template <class S>
+__global__ void __launch_bounds__(256) fuse_weight_bwd_apply_kernel(const float* __restrict__ dout, const float* __restrict__ zw,
+                                                                    const float* __restrict__ coef_w, const float* __restrict__ d,
+                                                                    const float* __restrict__ bcw, float* __restrict__ dzw,
+                                                                    float* __restrict__ dd, int dd_accumulate, float* __restrict__ dimg,
+                                                                    int dimg_accumulate, long long n_pix, int c) {
+    const int c4n = c >> 2;
+    const int cg = threadIdx.x % c4n;
+    const int pl = threadIdx.x / c4n;
+    const int ppb = 256 / c4n;
+    const Coef4 kw = load_coef(coef_w, c, cg);
+    const f32x4 w0 = *reinterpret_cast<const f32x4*>(bcw + cg * 4);
+    const f32x4 w1 = *reinterpret_cast<const f32x4*>(bcw + c + cg * 4);
+    const long long stride = (long long)gridDim.x * ppb;
+    const bool dd_acc = dd != nullptr && dd_accumulate, dimg_acc = dimg != nullptr && dimg_accumulate;
+    auto one = [&](f32x4 g, f32x4 a, f32x4 dv, f32x4 dd_old, f32x4 dimg_old, size_t i) {
+        const f32x4 yw = a * kw.scale + kw.shift;
+        const f32x4 xw = (a - kw.mean) * kw.invstd;
+        f32x4 rw, rd;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float sg = 1.f / (1.f + expf(-yw[j]));
+            const float gw = g[j] * dv[j] * sg * (1.f - sg);
+            rw[j] = kw.scale[j] * (gw - w0[j] - xw[j] * w1[j]);
+            rd[j] = g[j] * sg;
+        }
+        st4<S>(dzw, i, rw);
+        if (dd != nullptr) st4<S>(dd, i, dd_acc ? rd + dd_old : rd);
+        if (dimg != nullptr) st4<S>(dimg, i, dimg_acc ? g + dimg_old : g);
+    };
+    // one pixel per trip, like fuse_bwd_apply_kernel (five reads, three writes: the EW_U-unrolled form measured 5.10 against 5.24 TB/s)
+    for (long long p = (long long)blockIdx.x * ppb + pl; p < n_pix; p += stride) {
+        const size_t i = (size_t)p * c + cg * 4;
+        const f32x4 g = ld4<S>(dout, i);
+        one(g, ld4<S>(zw, i), ld4<S>(d, i), dd_acc ? ld4<S>(dd, i) : g, dimg_acc ? ld4<S>(dimg, i) : g, i);
+    }
+}
+
+// The channel interleave out[p] = [a[p] | b[p]] and its backward as ONE linear stream over the interleaved tensor `cat` [n_pix][ca + cb]:
+// lane i owns the i-th 16-byte group of cat (so the wide side is read or written in order, whole cache lines per wave) and finds its
+// group in a or b from (pixel, group within the row) -- (ca + cb) / 4 is 12, 24, 48, 96, not a power of two, so the pair comes from one
+// division per trip and is advanced by 256 groups per unrolled step.  A workgroup's EW_U groups per lane are consecutive 4-KB pieces.
+// FWD: cat = [a | b].  Backward: a (+)= cat[:, :ca], b (+)= cat[:, ca:]; a null a / b is skipped.
+// (Measured against a form that walked each source with its own power-of-two thread mapping -- strided 64 / 128-byte pieces of cat:
+// profiles/fusion_types_kernels.md.)
+template <class S, bool FWD>
+__global__ void __launch_bounds__(256) concat_kernel(float* __restrict__ a, int a_accumulate, float* __restrict__ b, int b_accumulate,
+                                                     float* __restrict__ cat, long long n_pix, int ca, int cb,
+                                                     const float* __restrict__ amax_a, const float* __restrict__ amax_b,
+                                                     float* __restrict__ amax_out) {
+    const int c4a = ca >> 2, c4t = (ca + cb) >> 2;
+    const long long total = n_pix * c4t;
+    const int dq = 256 / c4t, dr = 256 % c4t;
+    constexpr int TRIP = 256 * EW_U;
+    for (long long base = (long long)blockIdx.x * TRIP; base < total; base += (long long)gridDim.x * TRIP) {
+        const long long i0 = base + threadIdx.x;
+        long long p = i0 / c4t;
+        int g = (int)(i0 - p * c4t);
+        if (base + TRIP <= total) {   // (uniform) a whole trip: every load issued before the first store, no guards
+            f32x4 v[EW_U], old[EW_U];
+            float* side[EW_U];
+            size_t off[EW_U];
+#pragma unroll
+            for (int u = 0; u < EW_U; ++u) {
+                const bool in_a = g < c4a;
+                side[u] = in_a ? a : b;
+                off[u] = in_a ? (size_t)p * ca + g * 4 : (size_t)p * cb + (g - c4a) * 4;
+                if (FWD) {
+                    v[u] = ld4<S>(side[u], off[u]);
+                } else if (side[u] != nullptr) {
+                    v[u] = ld4<S>(cat, (size_t)(i0 + u * 256) * 4);
+                    old[u] = (in_a ? a_accumulate : b_accumulate) ? ld4<S>(side[u], off[u]) : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+                g += dr;
+                p += dq;
+                if (g >= c4t) { g -= c4t; ++p; }
+            }
+#pragma unroll
+            for (int u = 0; u < EW_U; ++u) {
+                if (FWD) st4<S>(cat, (size_t)(i0 + u * 256) * 4, v[u]);
+                else if (side[u] != nullptr) st4<S>(side[u], off[u], v[u] + old[u]);
+            }
+        } else {                      // the tensor's last, partial trip: one group at a time
+#pragma unroll 1
+            for (long long i = i0; i < total; i += 256) {
+                const bool in_a = g < c4a;
+                float* side = in_a ? a : b;
+                const size_t off = in_a ? (size_t)p * ca + g * 4 : (size_t)p * cb + (g - c4a) * 4;
+                if (FWD) {
+                    st4<S>(cat, (size_t)i * 4, ld4<S>(side, off));
+                } else if (side != nullptr) {
+                    f32x4 v = ld4<S>(cat, (size_t)i * 4);
+                    if (in_a ? a_accumulate : b_accumulate) v += ld4<S>(side, off);
+                    st4<S>(side, off, v);
+                }
+                g += dr;
+                p += dq;
+                if (g >= c4t) { g -= c4t; ++p; }
+            }
+        }
+    }
+    // amax_out (fp32 tensors): max(*amax_a, *amax_b) -- the maximum of the interleaved tensor is known from its sources', no pass over it
+    if (FWD && amax_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+        atomicMax(reinterpret_cast<unsigned*>(amax_out), __float_as_uint(fmaxf(rcf_abs_finite(*amax_a), rcf_abs_finite(*amax_b))));
 }
 
 template <class S>
@@ -580,6 +802,77 @@ static int fuse_fwd_impl(const float* zw, const float* coef_w, const float* zp, 
     return rcf_launch_status();
 }
 
+template <class S, bool AM = false>
+static int fuse_add_fwd_impl(const float* z, const float* coef, const float* img, float* out, long long n_pix, int c, void* stream,
+                             float* amax = nullptr) {
+    if (!z || !coef || !img || !out || n_pix <= 0 || (AM && !amax)) return RCF_EINVAL;
+    if (!c4_ok(c)) return RCF_EUNSUPPORTED;
+    hipLaunchKernelGGL((fuse_add_fwd_kernel<S, AM>), dim3(ew_blocks(n_pix, c)), dim3(256), 0, (hipStream_t)stream, z, coef, img, out,
+                       n_pix, c, amax);
+    return rcf_launch_status();
+}
+
+template <class S, bool AM = false>
+static int fuse_weight_fwd_impl(const float* zw, const float* coef_w, const float* d, const float* img, float* out, long long n_pix,
+                                int c, void* stream, float* amax = nullptr) {
+    if (!zw || !coef_w || !d || !img || !out || n_pix <= 0 || (AM && !amax)) return RCF_EINVAL;
+    if (!c4_ok(c)) return RCF_EUNSUPPORTED;
+    hipLaunchKernelGGL((fuse_weight_fwd_kernel<S, AM>), dim3(ew_blocks(n_pix, c)), dim3(256), 0, (hipStream_t)stream, zw, coef_w, d, img,
+                       out, n_pix, c, amax);
+    return rcf_launch_status();
+}
+
+template <class S>
+static int fuse_weight_bwd_reduce_impl(const float* dout, const float* zw, const float* coef_w, const float* d, double* partials,
+                                       long long n_pix, int c, void* stream) {
+    if (!dout || !zw || !coef_w || !d || !partials || n_pix <= 0) return RCF_EINVAL;
+    if (!c4_ok(c)) return RCF_EUNSUPPORTED;
+    const int ppb = 256 / (c >> 2);
+    hipLaunchKernelGGL((fuse_weight_bwd_reduce_kernel<S>), dim3(ew_blocks(n_pix, c)), dim3(256), (size_t)ppb * 2 * c * sizeof(double),
+                       (hipStream_t)stream, dout, zw, coef_w, d, partials, n_pix, c);
+    return rcf_launch_status();
+}
+
+template <class S>
+static int fuse_weight_bwd_apply_impl(const float* dout, const float* zw, const float* coef_w, const float* d, const float* bcoef_w,
+                                      float* dzw, float* dd, int dd_accumulate, float* dimg, int dimg_accumulate, long long n_pix, int c,
+                                      void* stream) {
+    if (!dout || !zw || !coef_w || !d || !bcoef_w || !dzw || n_pix <= 0) return RCF_EINVAL;
+    if (!c4_ok(c)) return RCF_EUNSUPPORTED;
+    hipLaunchKernelGGL((fuse_weight_bwd_apply_kernel<S>), dim3(ew_blocks(n_pix, c)), dim3(256), 0, (hipStream_t)stream, dout, zw, coef_w,
+                       d, bcoef_w, dzw, dd, dd_accumulate, dimg, dimg_accumulate, n_pix, c);
+    return rcf_launch_status();
+}
+
+// channel counts: multiples of 4 (one 16-byte group never straddles the two sources)
+static bool concat_ok(int ca, int cb) { return ca >= 4 && cb >= 4 && !(ca & 3) && !(cb & 3) && ca + cb <= 4096; }
+
+static int concat_blocks(long long n_pix, int ca, int cb) {
+    const long long per = 256 * EW_U, b = (n_pix * ((ca + cb) >> 2) + per - 1) / per;
+    return (int)(b > EW_MAX_BLOCKS ? EW_MAX_BLOCKS : b);
+}
+
+template <class S>
+static int concat_fwd_impl(const float* a, const float* b, float* out, long long n_pix, int ca, int cb, const float* amax_a,
+                           const float* amax_b, float* amax_out, void* stream) {
+    if (!a || !b || !out || n_pix <= 0 || ca <= 0 || cb <= 0 || (amax_out && (!amax_a || !amax_b))) return RCF_EINVAL;
+    if (!concat_ok(ca, cb)) return RCF_EUNSUPPORTED;
+    hipLaunchKernelGGL((concat_kernel<S, true>), dim3(concat_blocks(n_pix, ca, cb)), dim3(256), 0, (hipStream_t)stream,
+                       const_cast<float*>(a), 0, const_cast<float*>(b), 0, out, n_pix, ca, cb, amax_a, amax_b, amax_out);
+    return rcf_launch_status();
+}
+
+template <class S>
+static int concat_bwd_impl(const float* dout, float* da, int da_accumulate, float* db, int db_accumulate, long long n_pix, int ca, int cb,
+                           void* stream) {
+    if (!dout || (!da && !db) || n_pix <= 0 || ca <= 0 || cb <= 0) return RCF_EINVAL;
+    if (!concat_ok(ca, cb)) return RCF_EUNSUPPORTED;
+    hipLaunchKernelGGL((concat_kernel<S, false>), dim3(concat_blocks(n_pix, ca, cb)), dim3(256), 0, (hipStream_t)stream, da,
+                       da_accumulate, db, db_accumulate, const_cast<float*>(dout), n_pix, ca, cb, (const float*)nullptr,
+                       (const float*)nullptr, (float*)nullptr);
+    return rcf_launch_status();
+}
+
 template <class S>
 static int bn_act_bwd_reduce_impl(const float* dout, const float* z, const float* coef, const float* out, double* partials,
                                      long long n_pix, int c, int act, int has_res, void* stream) {
@@ -688,6 +981,32 @@ extern "C" int rcf_fuse_fwd(const float* zw, const float* coef_w, const float* z
                             float* out, long long n_pix, int c, void* stream) { return fuse_fwd_impl<StF32>(zw, coef_w, zp, coef_p, img, out, n_pix, c, stream); }
 extern "C" int rcf_fuse_fwd_b16(const float* zw, const float* coef_w, const float* zp, const float* coef_p, const float* img,
                             float* out, long long n_pix, int c, void* stream) { return fuse_fwd_impl<StB16>(zw, coef_w, zp, coef_p, img, out, n_pix, c, stream); }
+extern "C" int rcf_fuse_add_fwd(const float* z, const float* coef, const float* img, float* out, long long n_pix, int c,
+                                void* stream) { return fuse_add_fwd_impl<StF32>(z, coef, img, out, n_pix, c, stream); }
+extern "C" int rcf_fuse_add_fwd_b16(const float* z, const float* coef, const float* img, float* out, long long n_pix, int c,
+                                void* stream) { return fuse_add_fwd_impl<StB16>(z, coef, img, out, n_pix, c, stream); }
+extern "C" int rcf_fuse_weight_fwd(const float* zw, const float* coef_w, const float* d, const float* img, float* out, long long n_pix,
+                                   int c, void* stream) { return fuse_weight_fwd_impl<StF32>(zw, coef_w, d, img, out, n_pix, c, stream); }
+extern "C" int rcf_fuse_weight_fwd_b16(const float* zw, const float* coef_w, const float* d, const float* img, float* out, long long n_pix,
+                                   int c, void* stream) { return fuse_weight_fwd_impl<StB16>(zw, coef_w, d, img, out, n_pix, c, stream); }
+extern "C" int rcf_fuse_weight_bwd_reduce(const float* dout, const float* zw, const float* coef_w, const float* d, double* partials,
+                                          long long n_pix, int c, void* stream) { return fuse_weight_bwd_reduce_impl<StF32>(dout, zw, coef_w, d, partials, n_pix, c, stream); }
+extern "C" int rcf_fuse_weight_bwd_reduce_b16(const float* dout, const float* zw, const float* coef_w, const float* d, double* partials,
+                                          long long n_pix, int c, void* stream) { return fuse_weight_bwd_reduce_impl<StB16>(dout, zw, coef_w, d, partials, n_pix, c, stream); }
+extern "C" int rcf_fuse_weight_bwd_apply(const float* dout, const float* zw, const float* coef_w, const float* d, const float* bcoef_w,
+                                         float* dzw, float* dd, int dd_accumulate, float* dimg, int dimg_accumulate, long long n_pix,
+                                         int c, void* stream) { return fuse_weight_bwd_apply_impl<StF32>(dout, zw, coef_w, d, bcoef_w, dzw, dd, dd_accumulate, dimg, dimg_accumulate, n_pix, c, stream); }
+extern "C" int rcf_fuse_weight_bwd_apply_b16(const float* dout, const float* zw, const float* coef_w, const float* d, const float* bcoef_w,
+                                         float* dzw, float* dd, int dd_accumulate, float* dimg, int dimg_accumulate, long long n_pix,
+                                         int c, void* stream) { return fuse_weight_bwd_apply_impl<StB16>(dout, zw, coef_w, d, bcoef_w, dzw, dd, dd_accumulate, dimg, dimg_accumulate, n_pix, c, stream); }
+extern "C" int rcf_concat_fwd(const float* a, const float* b, float* out, long long n_pix, int ca, int cb, const float* amax_a,
+                              const float* amax_b, float* amax_out, void* stream) { return concat_fwd_impl<StF32>(a, b, out, n_pix, ca, cb, amax_a, amax_b, amax_out, stream); }
+extern "C" int rcf_concat_fwd_b16(const float* a, const float* b, float* out, long long n_pix, int ca, int cb, const float* amax_a,
+                              const float* amax_b, float* amax_out, void* stream) { return concat_fwd_impl<StB16>(a, b, out, n_pix, ca, cb, amax_a, amax_b, amax_out, stream); }
+extern "C" int rcf_concat_bwd(const float* dout, float* da, int da_accumulate, float* db, int db_accumulate, long long n_pix, int ca,
+                              int cb, void* stream) { return concat_bwd_impl<StF32>(dout, da, da_accumulate, db, db_accumulate, n_pix, ca, cb, stream); }
+extern "C" int rcf_concat_bwd_b16(const float* dout, float* da, int da_accumulate, float* db, int db_accumulate, long long n_pix, int ca,
+                              int cb, void* stream) { return concat_bwd_impl<StB16>(dout, da, da_accumulate, db, db_accumulate, n_pix, ca, cb, stream); }
 extern "C" int rcf_bn_act_bwd_reduce(const float* dout, const float* z, const float* coef, const float* out, double* partials,
                                      long long n_pix, int c, int act, int has_res, void* stream) { return bn_act_bwd_reduce_impl<StF32>(dout, z, coef, out, partials, n_pix, c, act, has_res, stream); }
 extern "C" int rcf_bn_act_bwd_reduce_b16(const float* dout, const float* z, const float* coef, const float* out, double* partials,
@@ -727,3 +1046,7 @@ extern "C" int rcf_bn_act_bwd_apply_amax(const float* dout, const float* z, cons
                                          float* amax, void* stream) { return bn_act_bwd_apply_impl<StF32, true>(dout, z, coef, out, bcoef, dz, dres, dres_accumulate, n_pix, c, act, has_res, stream, amax); }
 extern "C" int rcf_head_bn_bwd_apply_amax(const float* dlogit, const float* w_head, const float* z, const float* coef, const float* bcoef,
                                           float* dz, int n, int h, int w, int c, float* amax, void* stream) { return head_bn_bwd_apply_impl<StF32, true>(dlogit, w_head, z, coef, bcoef, dz, n, h, w, c, stream, amax); }
+extern "C" int rcf_fuse_add_fwd_amax(const float* z, const float* coef, const float* img, float* out, long long n_pix, int c,
+                                     float* amax, void* stream) { return fuse_add_fwd_impl<StF32, true>(z, coef, img, out, n_pix, c, stream, amax); }
+extern "C" int rcf_fuse_weight_fwd_amax(const float* zw, const float* coef_w, const float* d, const float* img, float* out,
+                                        long long n_pix, int c, float* amax, void* stream) { return fuse_weight_fwd_impl<StF32, true>(zw, coef_w, d, img, out, n_pix, c, stream, amax); }

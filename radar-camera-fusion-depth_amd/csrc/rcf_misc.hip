@@ -387,12 +387,14 @@ __global__ void __launch_bounds__(256) head_fwd_mfma_b16_kernel(const float* __r
 // A operand as they lie in memory, both weight matrices (scaled by their BatchNorm scale while they are loaded) live in registers for
 // the wave's lifetime, no LDS, no barrier; blockIdx.y takes 32 NT output channels.  The D fragments of the two products have the
 // same (pixel, channel) layout, so the gate needs no exchange; pairs of lanes swap one value to store one dword per pixel pair.
+// NB = 1 is the 'add' fusion (src/networks.py:857-859) in the same form: out = BN_p(W2 d) + img -- one product, no gate (w1 / coef_w
+// are not read).
 template <int CTRL>
 __device__ __forceinline__ unsigned hd_dpp_u32(unsigned v) {
     return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
 }
 
-template <int KST, int NT, int MT>
+template <int KST, int NT, int MT, int NB = 2>
 __global__ void __launch_bounds__(256, 2) fuse_wp_b16_kernel(const unsigned short* __restrict__ d, const float* __restrict__ w1,
                                                              const float* __restrict__ coef_w, const float* __restrict__ w2,
                                                              const float* __restrict__ coef_p, const unsigned short* __restrict__ img,
@@ -402,11 +404,11 @@ __global__ void __launch_bounds__(256, 2) fuse_wp_b16_kernel(const unsigned shor
     const int li = lane & 31, lh = lane >> 5, odd = li & 1;
     const int co0 = blockIdx.y * 32 * NT;
     // B fragments: lane (li = output channel, lh), k index e of step s <-> input channel 16 s + 8 lh + e of OIHW [co][ci][1][1]
-    hd_bf16x8 bw[2][KST][NT];
+    hd_bf16x8 bw[NB][KST][NT];
 #pragma unroll
-    for (int br = 0; br < 2; ++br) {
-        const float* w = br ? w2 : w1;
-        const float* coef = br ? coef_p : coef_w;
+    for (int br = 0; br < NB; ++br) {
+        const float* w = (br || NB == 1) ? w2 : w1;
+        const float* coef = (br || NB == 1) ? coef_p : coef_w;
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) {
             const int co = co0 + ni * 32 + li;
@@ -429,7 +431,7 @@ __global__ void __launch_bounds__(256, 2) fuse_wp_b16_kernel(const unsigned shor
         const int cp = (co0 + ni * 32 + li) & ~1;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            sw[ni][e] = cp + e < c_i ? coef_w[c_i + cp + e] : 0.f;
+            sw[ni][e] = (NB == 2 && cp + e < c_i) ? coef_w[c_i + cp + e] : 0.f;
             sp[ni][e] = cp + e < c_i ? coef_p[c_i + cp + e] : 0.f;
         }
     }
@@ -460,9 +462,9 @@ __global__ void __launch_bounds__(256, 2) fuse_wp_b16_kernel(const unsigned shor
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const long long pb0 = (blk0 + mt) * 32;
-            f32x16 acc[2][NT];
+            f32x16 acc[NB][NT];
 #pragma unroll
-            for (int br = 0; br < 2; ++br)
+            for (int br = 0; br < NB; ++br)
 #pragma unroll
                 for (int ni = 0; ni < NT; ++ni) {
 #pragma unroll
@@ -479,9 +481,9 @@ __global__ void __launch_bounds__(256, 2) fuse_wp_b16_kernel(const unsigned shor
 #pragma unroll
                 for (int ni = 0; ni < NT; ++ni) {
                     const int cp = (co0 + ni * 32 + li) & ~1;
-                    float v[2][2];   // [branch][channel cp, cp + 1] at pixel p
+                    float v[NB][2];   // [branch][channel cp, cp + 1] at pixel p
 #pragma unroll
-                    for (int br = 0; br < 2; ++br) {
+                    for (int br = 0; br < NB; ++br) {
                         const float a0 = acc[br][ni][rj], a1 = acc[br][ni][rj + 1];
                         const float mine = odd ? a1 : a0, give = odd ? a0 : a1;
                         const float got = __uint_as_float(hd_dpp_u32<0xB1>(__float_as_uint(give)));
@@ -491,10 +493,16 @@ __global__ void __launch_bounds__(256, 2) fuse_wp_b16_kernel(const unsigned shor
                     const float i0 = __uint_as_float(iw[mt][g][ni] << 16), i1 = __uint_as_float(iw[mt][g][ni] & 0xffff0000u);
                     // the gate on the hardware's exp2 / reciprocal (1 ulp each; the result is rounded to 8 bits): libm's expf and an IEEE
                     // division are ~30 VALU instructions per element, which made this HBM kernel VALU-bound
-                    const float g0 = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504f * (v[0][0] + sw[ni][0])));
-                    const float g1 = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504f * (v[0][1] + sw[ni][1])));
-                    const float o0 = g0 * (v[1][0] + sp[ni][0]) + i0;
-                    const float o1 = g1 * (v[1][1] + sp[ni][1]) + i1;
+                    float o0, o1;
+                    if constexpr (NB == 2) {
+                        const float g0 = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504f * (v[0][0] + sw[ni][0])));
+                        const float g1 = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504f * (v[0][1] + sw[ni][1])));
+                        o0 = g0 * (v[NB - 1][0] + sp[ni][0]) + i0;
+                        o1 = g1 * (v[NB - 1][1] + sp[ni][1]) + i1;
+                    } else {
+                        o0 = v[0][0] + sp[ni][0] + i0;
+                        o1 = v[0][1] + sp[ni][1] + i1;
+                    }
                     if (p < npix && cp < c_i) *reinterpret_cast<unsigned*>(out + (size_t)p * c_i + cp) = rcf_f2b2(o0, o1);
                 }
             }
@@ -1519,7 +1527,7 @@ extern "C" int rcf_upsample_nearest_bwd_b16(const float* dup, float* dsrc, int d
                                         int h_src, int w_src, int c, void* stream) { return upsample_nearest_bwd_impl<StB16>(dup, dsrc, dsrc_accumulate, n, h_up, w_up, h_src, w_src, c, stream); }
 extern "C" int rcf_head_fwd(const float* x, const float* w, float* logit, float* depth, int n, int h, int w_, int c,
                             float min_depth, float max_depth, void* stream) { return head_fwd_impl<StF32>(x, w, logit, depth, n, h, w_, c, min_depth, max_depth, stream); }
-template <int KST, int NT, int MT>
+template <int KST, int NT, int MT, int NB = 2>
 static int launch_fuse_wp(const float* d, const float* w1, const float* coef_w, const float* w2, const float* coef_p, const float* img,
                           float* out, long long n_pix, int c_i, void* stream) {
     const int gy = (c_i + 32 * NT - 1) / (32 * NT);
@@ -1534,7 +1542,7 @@ static int launch_fuse_wp(const float* d, const float* w1, const float* coef_w, 
     long long gx = (long long)ncu * 4 / gy;   // two workgroups per CU, two trips' worth of slack (pw_grid of the 1x1 kernel)
     if (gx > trips) gx = trips;
     if (gx < 1) gx = 1;
-    hipLaunchKernelGGL((fuse_wp_b16_kernel<KST, NT, MT>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((fuse_wp_b16_kernel<KST, NT, MT, NB>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const unsigned short*>(d), w1, coef_w, w2, coef_p, reinterpret_cast<const unsigned short*>(img),
                        reinterpret_cast<unsigned short*>(out), n_pix, c_i);
     return rcf_launch_status();
@@ -1553,6 +1561,18 @@ extern "C" int rcf_fuse_wp_infer_b16(const float* d, const float* w1, const floa
         case 32: return launch_fuse_wp<2, 2, 1>(d, w1, coef_w, w2, coef_p, img, out, n_pix, c_i, stream);
         case 64: return launch_fuse_wp<4, 2, 1>(d, w1, coef_w, w2, coef_p, img, out, n_pix, c_i, stream);
         default: return launch_fuse_wp<8, 1, 1>(d, w1, coef_w, w2, coef_p, img, out, n_pix, c_i, stream);
+    }
+}
+
+extern "C" int rcf_fuse_add_infer_b16(const float* d, const float* w, const float* coef, const float* img, float* out, long long n_pix,
+                                      int c_d, int c_i, void* stream) {
+    if (!d || !w || !coef || !img || !out || n_pix <= 0) return RCF_EINVAL;
+    if (!rcf_fuse_wp_infer_supported(c_d, c_i)) return RCF_EUNSUPPORTED;
+    switch (c_d) {   // the tilings of rcf_fuse_wp_infer_b16: the same A operand and image traffic, half the weights
+        case 16: return launch_fuse_wp<1, 1, 4, 1>(d, w, coef, w, coef, img, out, n_pix, c_i, stream);
+        case 32: return launch_fuse_wp<2, 2, 1, 1>(d, w, coef, w, coef, img, out, n_pix, c_i, stream);
+        case 64: return launch_fuse_wp<4, 2, 1, 1>(d, w, coef, w, coef, img, out, n_pix, c_i, stream);
+        default: return launch_fuse_wp<8, 1, 1, 1>(d, w, coef, w, coef, img, out, n_pix, c_i, stream);
     }
 }
 

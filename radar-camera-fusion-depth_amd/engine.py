@@ -1160,6 +1160,138 @@ class Engine(object):
             self.tape.append(backward)
         return out
 
+    def fuse_add(self, layer_p, dep, img):
+        '''conv_project + image (src/networks.py:857-859): BN(W d) + img.  The backward is a plain BatchNorm backward on dout (the
+        BatchNorm passes with a linear activation) and dimg += dout.'''
+        if (self.fuse_eval and not self.training and self.tape is None and self.fuse_wp_one_pass and layer_p.kernel_size == 1
+                and layer_p.stride == 1):
+            # inference on bf16 tensors: the 1x1 convolution, the affine BatchNorm and the sum in one streaming kernel
+            # (rcf_fuse_add_infer_b16, the sibling of the 'weight_and_project' form in fuse())
+            dt, it = self._mat(dep), self._mat(img)
+            if (dt.dtype == torch.bfloat16 and it.dtype == torch.bfloat16 and tuple(dt.shape[:3]) == tuple(it.shape[:3])
+                    and ops.fuse_wp_infer_supported(dt.shape[3], it.shape[3])):
+                out = Act(torch.empty_like(it))
+                ops.fuse_add_infer(dt, layer_p.conv.weight.detach(), self._bn_coef_eval(layer_p, it), it, out.t)
+                return out
+        zp, rec_p, pp = self._conv(layer_p, dep, want_stats=self.training)
+        coef_p = self._bn_coef(layer_p, pp, rec_p, zp)
+        n_pix = zp.shape[0] * zp.shape[1] * zp.shape[2]
+        c = zp.shape[3]
+        out = Act(torch.empty_like(zp))
+        out.amax = self._amax_slot() if zp.dtype == torch.float32 else None
+        ops.fuse_add_fwd(zp, coef_p, self._mat(img), out.t, n_pix, c, amax=out.amax)
+        if self.tape is not None:
+            bnp = layer_p.batch_norm
+            batch_stats = self.training
+            scope = self._scope
+
+            def backward():
+                self._set_scope(scope)
+                dout = out.g
+                nb = ops.ew_blocks(n_pix, c)
+                bpart = torch.empty((nb, 2, c), dtype=torch.float64, device=zp.device)
+                ops.bn_act_bwd_reduce(dout, zp, coef_p, None, bpart, n_pix, c, RCF_ACT_NONE, False)
+                bcp = self._newf((2, c), zp)
+                ops.bn_bwd_finalize(bpart, nb, 2 * c, c, n_pix, bcp, self.grad_of(bnp.weight), self.grad_of(bnp.bias))
+                if not batch_stats:
+                    bcp.zero_()
+                self._wgrad_done(bnp.weight, bnp.bias)
+                dzp = torch.empty_like(zp)
+                ops.bn_act_bwd_apply(dout, zp, coef_p, None, bcp, dzp, None, False, n_pix, c, RCF_ACT_NONE, False)
+                if img.needs_grad:
+                    dimg_acc = self._grad_target(img)
+                    ops.convert(dout, img.g, accumulate=dimg_acc)
+                out.g = None
+                # the 1x1 convolution's backward writes the DEPTH branch's gradient: on that branch's stream when it has one
+                br = self._branch_enter(first_wait=True)
+                if br is not None:
+                    self._side_keep.extend((dzp, zp))
+                self._conv_backward(layer_p, rec_p, dep, None, dzp)
+                self._branch_exit(br)
+
+            self.tape.append(backward)
+        return out
+
+    def fuse_weight(self, layer_w, dep, img):
+        '''conv_weight * depth + image (src/networks.py:860-862): sigmoid(BN(W * d)) * d + img, W a 3x3 convolution c_d -> c_d.  The
+        depth activation has three consumers: the next block, the gate convolution and the gate product.'''
+        zw, rec_w, pw = self._conv(layer_w, dep, want_stats=self.training)
+        coef_w = self._bn_coef(layer_w, pw, rec_w, zw)
+        n_pix = zw.shape[0] * zw.shape[1] * zw.shape[2]
+        c = zw.shape[3]
+        out = Act(torch.empty_like(zw))
+        out.amax = self._amax_slot() if zw.dtype == torch.float32 else None
+        ops.fuse_weight_fwd(zw, coef_w, self._mat(dep), self._mat(img), out.t, n_pix, c, amax=out.amax)
+        if self.tape is not None:
+            bnw = layer_w.batch_norm
+            batch_stats = self.training
+            scope = self._scope
+
+            def backward():
+                self._set_scope(scope)
+                dout = out.g
+                nb = ops.ew_blocks(n_pix, c)
+                bpart = torch.empty((nb, 2, c), dtype=torch.float64, device=zw.device)
+                ops.fuse_weight_bwd_reduce(dout, zw, coef_w, dep.t, bpart, n_pix, c)
+                bcw = self._newf((2, c), zw)
+                ops.bn_bwd_finalize(bpart, nb, 2 * c, c, n_pix, bcw, self.grad_of(bnw.weight), self.grad_of(bnw.bias))
+                if not batch_stats:
+                    bcw.zero_()
+                self._wgrad_done(bnw.weight, bnw.bias)
+                dzw = torch.empty_like(zw)
+                # the second pass adds into BOTH branches' gradients.  The depth branch's is being written on that branch's stream, so
+                # the pass runs there (after the main stream's work so far: dout, the image branch's gradient), and the main stream
+                # waits for it -- not for the gate convolution's backward behind it -- before it touches the image gradient again
+                dimg_acc = self._grad_target(img) if img.needs_grad else False   # (allocated on the main stream, which frees it)
+                br = self._branch_enter(first_wait=True)
+                if br is not None:
+                    self._side_keep.extend((dout, dzw, zw))
+                dd_acc =self._grad_target(dep) if dep.needs_grad else False
+                ops.fuse_weight_bwd_apply(dout, zw, coef_w, dep.t, bcw, dzw, dep.g if dep.needs_grad else None, dd_acc,
+                                          img.g if img.needs_grad else None, dimg_acc, n_pix, c)
+                done = torch.cuda.current_stream().record_event() if br is not None else None
+                out.g = None
+                self._conv_backward(layer_w, rec_w, dep, None, dzw)
+                self._branch_exit(br)
+                if done is not None:
+                    torch.cuda.current_stream().wait_event(done)
+
+            self.tape.append(backward)
+        return out
+
+    def fuse_concat(self, dep, img, depth_first):
+        '''torch.cat([img, d], 1) -- at level 1 torch.cat([d, img], 1) (src/networks.py:892 against :868).  The fused tensor is
+        materialised (it is the second source of a decoder convolution / the one source of the first up-convolution); its maximum is
+        the larger of its sources'.'''
+        a, b = (dep, img) if depth_first else (img, dep)
+        at, bt = self._mat(a), self._mat(b)
+        ca, cb = at.shape[3], bt.shape[3]
+        out = Act(self._new(tuple(at.shape[:3]) + (ca + cb,), at))
+        if at.dtype == torch.float32 and a.amax is not None and b.amax is not None:
+            out.amax = self._amax_slot()
+        ops.concat_fwd(at, bt, out.t, None if out.amax is None else (a.amax, b.amax, out.amax))
+        if self.tape is not None:
+            def backward():
+                dout = out.g
+                out.g = None
+                if dout is None:
+                    return
+                # each branch's slice on that branch's stream: the image branch's gradient here, the depth branch's on its own stream
+                img_first = not depth_first
+                if img.needs_grad:
+                    acc = self._grad_target(img)
+                    ops.concat_bwd(dout, img.g if img_first else None, acc, None if img_first else img.g, acc, ca, cb)
+                if dep.needs_grad:
+                    br = self._branch_enter(first_wait=True)
+                    if br is not None:
+                        self._side_keep.append(dout)
+                    acc = self._grad_target(dep)
+                    ops.concat_bwd(dout, None if img_first else dep.g, acc, dep.g if img_first else None, acc, ca, cb)
+                    self._branch_exit(br)
+
+            self.tape.append(backward)
+        return out
+
     def max_pool(self, x):
         '''torch.nn.MaxPool2d(3, 2, 1) (src/networks.py:392-395).'''
         xt = self._mat(x)
@@ -1265,7 +1397,7 @@ class Engine(object):
         br = self._branch_enter(first_wait=True)     # the depth branch: its own stream up to each level's fusion
         dep = self.conv_bn_act(enc.conv1_depth, self._input(depth_nhwc, depth_s2d, hw))
         self._branch_exit(br)
-        layers = [self._fuse_level(enc.conv1_weight, enc.conv1_project, dep, img)]
+        layers = [self._fuse_level(1, dep, img)]
         img = self.max_pool(img)
         br = self._branch_enter(first_wait=False)
         dep = self.max_pool(dep)
@@ -1276,7 +1408,7 @@ class Engine(object):
                 br = self._branch_enter(first_wait=False)
                 dep = self.resnet_block(blk_d, dep)
                 self._branch_exit(br)
-            layers.append(self._fuse_level(getattr(enc, 'conv%d_weight' % lvl), getattr(enc, 'conv%d_project' % lvl), dep, img))
+            layers.append(self._fuse_level(lvl, dep, img))
         if self.fuse_on_branch and self.branch_stream and self._branch_busy:   # the decoder reads the fused tensors: the main stream joins the branch here
             cur = torch.cuda.current_stream()
             cur.wait_stream(self._branch)
@@ -1289,19 +1421,33 @@ class Engine(object):
         tape, self.tape = self.tape, None
         return out, tape
 
-    def _fuse_level(self, layer_w, layer_p, dep, img):
+    def _fuse_one(self, lvl, dep, img):
+        """The fused tensor of level lvl under the encoder's fusion type (src/networks.py:857-870, repeated at every level)."""
+        enc = self.encoder
+        kind = enc.fusion_type
+        if kind == 'weight_and_project':
+            return self.fuse(getattr(enc, 'conv%d_weight' % lvl), getattr(enc, 'conv%d_project' % lvl), dep, img)
+        if kind == 'add':
+            return self.fuse_add(getattr(enc, 'conv%d_project' % lvl), dep, img)
+        if kind == 'weight':
+            return self.fuse_weight(getattr(enc, 'conv%d_weight' % lvl), dep, img)
+        if kind == 'concat':
+            return self.fuse_concat(dep, img, depth_first=lvl == 1)
+        raise ValueError('Unsupported fusion type on the HIP path: {}'.format(kind))
+
+    def _fuse_level(self, lvl, dep, img):
         '''One level's fusion.  Default: on the main stream once the depth branch has delivered `dep`.  fuse_on_branch: on the branch
         stream once the main stream has delivered `img` -- the main stream goes straight on to the next level's image block; the
         fusion's backward stays a main-stream closure (it adds into the image branch's gradient).'''
         if not (self.fuse_on_branch and self.branch_stream) or self.bn_on_load:
             self._branch_wait(dep)
-            return self.fuse(layer_w, layer_p, dep, img)
+            return self._fuse_one(lvl, dep, img)
         br = self._branch_enter(first_wait=True)
         if br is not None and img.t is not None:
             img.t.record_stream(self._branch)   # (inference: the image activation is freed by the main stream as soon as it moves on)
         self._tape_main = True
         try:
-            return self.fuse(layer_w, layer_p, dep, img)
+            return self._fuse_one(lvl, dep, img)
         finally:
             self._tape_main = False
             self._branch_exit(br)

@@ -203,12 +203,18 @@ class FusionNetModel(object):
                 conv_block(b.projection)
             conv_block(b.conv2)
 
+        def fusion(lvl):    # the fusion modules the encoder's type owns (networks.FusionNetEncoder): none for 'concat'
+            for kind in ('weight', 'project'):
+                layer = getattr(enc, 'conv%d_%s' % (lvl, kind), None)
+                if layer is not None:
+                    conv_block(layer)
+
         conv_block(enc.conv1_image); conv_block(enc.conv1_depth)
-        conv_block(enc.conv1_weight); conv_block(enc.conv1_project)
+        fusion(1)
         for lvl in range(2, enc.network_depth + 1):
             for bi, bd in zip(getattr(enc, 'blocks%d_image' % lvl), getattr(enc, 'blocks%d_depth' % lvl)):
                 res_block(bi); res_block(bd)
-            conv_block(getattr(enc, 'conv%d_weight' % lvl)); conv_block(getattr(enc, 'conv%d_project' % lvl))
+            fusion(lvl)
         for name in dec.block_names:
             blk = getattr(dec, name)
             conv_block(blk.deconv if blk.deconv_type == 'transpose' else blk.deconv.conv); conv_block(blk.conv)

@@ -12,8 +12,14 @@ from . import net_utils
 class FusionNetEncoder(net_utils._NoForward):
     '''
     src/networks.py:270-1005.  Two independent ResNet branches (image, depth); at each of the `network_depth`
-    levels the fused tensor  sigmoid(BN(W1 d)) * BN(W2 d) + img  is emitted as a skip / the latent
-    ('weight_and_project', :863-866).  The branches never see the fused tensors.
+    levels the fused tensor is emitted as a skip / the latent (:857-870, repeated per level); the branches never see the
+    fused tensors.  fusion_type selects it, and with it which convL_* modules exist (:350-389):
+      'weight_and_project'  sigmoid(BN(W1 d)) * BN(W2 d) + img    convL_weight, convL_project (1x1, c_d -> c_i)
+      'add'                 BN(W d) + img                         convL_project (1x1, c_d -> c_i); none at level 7 (:742)
+      'weight'              sigmoid(BN(W * d)) * d + img          convL_weight (3x3, c_d -> c_d), levels 1..5 only (:681, :742)
+      'concat'              cat([img, d]) -- level 1: cat([d, img]) (:868 against :892) -- no parameters
+    The envelopes are the reference's: 'weight' runs with five levels and equal branch widths, 'add' with five or six levels;
+    outside them the reference's forward fails, and this constructor raises ValueError naming the line.
     '''
 
     def __init__(self, n_layer=18, input_channels_image=3, input_channels_depth=3,
@@ -28,10 +34,8 @@ class FusionNetEncoder(net_utils._NoForward):
             n_blocks = [3, 4, 6, 3]
         else:
             raise ValueError('Only supports 18, 34 layer architecture')          # :311
-        if fusion_type != 'weight_and_project':
-            # the reference also has 'add', 'weight', 'concat' (:350-389); only the shipped flag
-            # (bash/train_fusionnet_nuscenes.sh:33) has a HIP fusion kernel
-            raise ValueError('Unsupported fusion type on the HIP path: {}'.format(fusion_type))
+        if fusion_type not in ('add', 'weight', 'weight_and_project', 'concat'):
+            raise ValueError('Unsupported fusion type: {}'.format(fusion_type))                # :870
         assert len(n_filters_encoder_image) == len(n_filters_encoder_depth)
         for n in range(len(n_filters_encoder_image) - len(n_blocks) - 1):            # :317-318
             n_blocks = n_blocks + [n_blocks[-1]]
@@ -39,6 +43,24 @@ class FusionNetEncoder(net_utils._NoForward):
         assert network_depth < 8, 'Does not support network depth of 8 or more'     # :322
         assert network_depth == len(n_blocks) + 1
         self.network_depth = network_depth
+        if fusion_type == 'add' and network_depth == 7:
+            # src/networks.py:742-760 builds conv7_weight / conv7_project for 'weight_and_project' only, so the reference's forward
+            # dies at :989 (AttributeError: conv7_project)
+            raise ValueError("fusion type 'add' supports at most 6 levels: the reference constructs no conv7_project "
+                             '(src/networks.py:742, :989)')
+        if fusion_type == 'weight' and network_depth > 5:
+            # :681-709 and :742-760 build level 6 / 7 fusion modules for 'add' / 'weight_and_project' only: the reference's forward dies
+            # at :970 (AttributeError: conv6_weight)
+            raise ValueError("fusion type 'weight' supports 5 levels: the reference constructs no conv6_weight / conv7_weight "
+                             '(src/networks.py:681, :742, :970)')
+        if fusion_type == 'weight' and list(n_filters_encoder_image) != list(n_filters_encoder_depth):
+            # conv_weight maps c_d -> c_d (:362-369) and its output multiplies the depth features and is added to the image features
+            # (:862): the reference fails in the broadcast unless the branches have equal widths
+            raise ValueError("fusion type 'weight' needs equal image and depth branch widths: conv_weight(depth) * depth + image "
+                             '(src/networks.py:862) does not broadcast otherwise')
+        has_w = fusion_type in ('weight', 'weight_and_project')       # which fusion modules a level owns (:350-389)
+        gate_k = 3 if fusion_type == 'weight' else 1                   # 'weight': a 3x3 convolution c_d -> c_d (:362-369)
+        has_p = fusion_type in ('add', 'weight_and_project')
         act = net_utils.activation_func(activation_func)
         fi, fd = list(n_filters_encoder_image), list(n_filters_encoder_depth)
         bn = use_batch_norm
@@ -46,8 +68,10 @@ class FusionNetEncoder(net_utils._NoForward):
 
         self.conv1_image = net_utils.Conv2d(input_channels_image, fi[0], 7, 2, wi, act, bn)     # :332
         self.conv1_depth = net_utils.Conv2d(input_channels_depth, fd[0], 7, 2, wi, act, bn)     # :341
-        self.conv1_weight = net_utils.Conv2d(fd[0], fi[0], 1, 1, wi, 'sigmoid', bn)             # :373
-        self.conv1_project = net_utils.Conv2d(fd[0], fi[0], 1, 1, wi, None, bn)                 # :382
+        if has_w:
+            self.conv1_weight = net_utils.Conv2d(fd[0], fd[0] if gate_k == 3 else fi[0], gate_k, 1, wi, 'sigmoid', bn)   # :362, :373
+        if has_p:
+            self.conv1_project = net_utils.Conv2d(fd[0], fi[0], 1, 1, wi, None, bn)             # :351, :382
         for lvl in range(2, 8):
             if lvl <= network_depth:
                 stride = 1 if lvl == 2 else 2                                                   # :414, :479
@@ -61,8 +85,10 @@ class FusionNetEncoder(net_utils._NoForward):
                     dep_blocks.append(net_utils.ResNetBlock(di if b == 0 else do, do, s, wi, act, bn))
                 setattr(self, 'blocks%d_image' % lvl, torch.nn.Sequential(*img_blocks))
                 setattr(self, 'blocks%d_depth' % lvl, torch.nn.Sequential(*dep_blocks))
-                setattr(self, 'conv%d_weight' % lvl, net_utils.Conv2d(do, co, 1, 1, wi, 'sigmoid', bn))
-                setattr(self, 'conv%d_project' % lvl, net_utils.Conv2d(do, co, 1, 1, wi, None, bn))
+                if has_w:
+                    setattr(self, 'conv%d_weight' % lvl, net_utils.Conv2d(do, do if gate_k == 3 else co, gate_k, 1, wi, 'sigmoid', bn))
+                if has_p:
+                    setattr(self, 'conv%d_project' % lvl, net_utils.Conv2d(do, co, 1, 1, wi, None, bn))
             elif lvl >= 6:                                                                      # :710-714, :761-765
                 setattr(self, 'blocks%d_image' % lvl, None)
                 setattr(self, 'blocks%d_depth' % lvl, None)

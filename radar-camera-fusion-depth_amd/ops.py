@@ -458,6 +458,57 @@ def fuse_fwd(zw, coef_w, zp, coef_p, img, out, n_pix, c, amax=None):
                                                 _stream()), 'rcf_fuse_fwd')
 
 
+def fuse_add_fwd(z, coef, img, out, n_pix, c, amax=None):
+    """The 'add' fusion: out = BN(z) + img (rcf_fuse_add_fwd); amax as in bn_act_fwd."""
+    if amax is not None:
+        check(_lib.load().rcf_fuse_add_fwd_amax(_f32(z), _f32(coef), _f32(img), _f32(out), n_pix, c, _f32(amax), _stream()),
+              'rcf_fuse_add_fwd_amax')
+        return
+    check(_fn('rcf_fuse_add_fwd', z, img, out)(_a(z), _f32(coef), _a(img), _a(out), n_pix, c, _stream()), 'rcf_fuse_add_fwd')
+
+
+def fuse_weight_fwd(zw, coef_w, d, img, out, n_pix, c, amax=None):
+    """The 'weight' fusion: out = sigmoid(BN(zw)) * d + img (rcf_fuse_weight_fwd); amax as in bn_act_fwd."""
+    if amax is not None:
+        check(_lib.load().rcf_fuse_weight_fwd_amax(_f32(zw), _f32(coef_w), _f32(d), _f32(img), _f32(out), n_pix, c, _f32(amax),
+                                                   _stream()), 'rcf_fuse_weight_fwd_amax')
+        return
+    check(_fn('rcf_fuse_weight_fwd', zw, d, img, out)(_a(zw), _f32(coef_w), _a(d), _a(img), _a(out), n_pix, c, _stream()),
+          'rcf_fuse_weight_fwd')
+
+
+def fuse_weight_bwd_reduce(dout, zw, coef_w, d, partials, n_pix, c):
+    check(_fn('rcf_fuse_weight_bwd_reduce', dout, zw, d)(_a(dout), _a(zw), _f32(coef_w), _a(d), _f64(partials), n_pix, c, _stream()),
+          'rcf_fuse_weight_bwd_reduce')
+
+
+def fuse_weight_bwd_apply(dout, zw, coef_w, d, bcoef_w, dzw, dd, dd_accumulate, dimg, dimg_accumulate, n_pix, c):
+    check(_fn('rcf_fuse_weight_bwd_apply', dout, zw, d, dzw, dd, dimg)(_a(dout), _a(zw), _f32(coef_w), _a(d), _f32(bcoef_w), _a(dzw),
+                                                                       _a(dd), 1 if dd_accumulate else 0, _a(dimg),
+                                                                       1 if dimg_accumulate else 0, n_pix, c, _stream()),
+          'rcf_fuse_weight_bwd_apply')
+
+
+def concat_fwd(a, b, out, amax=None):
+    """The 'concat' fusion: out[..., :ca] = a, out[..., ca:] = b (NHWC).  amax = (amax_a, amax_b, zeroed slot): the slot receives
+    the larger of the two sources' maxima."""
+    ca, cb = a.shape[-1], b.shape[-1]
+    if tuple(a.shape[:-1]) != tuple(b.shape[:-1]) or tuple(out.shape) != tuple(a.shape[:-1]) + (ca + cb,):
+        raise ValueError('concat_fwd: shapes disagree')
+    am = (None, None, None) if amax is None else amax
+    check(_fn('rcf_concat_fwd', a, b, out)(_a(a), _a(b), _a(out), a.numel() // ca, ca, cb, _f32(am[0]), _f32(am[1]), _f32(am[2]),
+                                           _stream()), 'rcf_concat_fwd')
+
+
+def concat_bwd(dout, da, da_accumulate, db, db_accumulate, ca, cb):
+    """da (+)= dout[..., :ca], db (+)= dout[..., ca:]; da or db may be None (skipped)."""
+    if dout.shape[-1] != ca + cb or (da is not None and tuple(da.shape) != tuple(dout.shape[:-1]) + (ca,)) \
+            or (db is not None and tuple(db.shape) != tuple(dout.shape[:-1]) + (cb,)):
+        raise ValueError('concat_bwd: shapes disagree')
+    check(_fn('rcf_concat_bwd', dout, da, db)(_a(dout), _a(da), 1 if da_accumulate else 0, _a(db), 1 if db_accumulate else 0,
+                                              dout.numel() // (ca + cb), ca, cb, _stream()), 'rcf_concat_bwd')
+
+
 def fuse_wp_infer_supported(c_d, c_i):
     return bool(_lib.load().rcf_fuse_wp_infer_supported(int(c_d), int(c_i)))
 
@@ -472,6 +523,17 @@ def fuse_wp_infer(d, w1, coef_w, w2, coef_p, img, out):
     n_pix = img.numel() // c_i
     check(_lib.load().rcf_fuse_wp_infer_b16(_a(d), _f32(w1), _f32(coef_w), _f32(w2), _f32(coef_p), _a(img), _a(out), n_pix, c_d, c_i,
                                             _stream()), 'rcf_fuse_wp_infer_b16')
+
+
+def fuse_add_infer(d, w, coef, img, out):
+    """Inference 'add' fusion in one pass (bf16 NHWC tensors): BN(W d) + img, eval-mode BN; widths as fuse_wp_infer_supported."""
+    if d.dtype != torch.bfloat16 or img.dtype != torch.bfloat16 or out.dtype != torch.bfloat16:
+        raise ValueError('fuse_add_infer takes bf16 activation tensors')
+    c_d, c_i = d.shape[-1], img.shape[-1]
+    if tuple(w.shape[:2]) != (c_i, c_d) or tuple(out.shape) != tuple(img.shape):
+        raise ValueError('fuse_add_infer: shapes disagree')
+    check(_lib.load().rcf_fuse_add_infer_b16(_a(d), _f32(w), _f32(coef), _a(img), _a(out), img.numel() // c_i, c_d, c_i, _stream()),
+          'rcf_fuse_add_infer_b16')
 
 
 def ew_blocks(n_pix, c):

@@ -122,6 +122,20 @@ TINY = dict(
     n_filters_decoder=[32, 32, 16, 8, 8, 4])
 '''SURVEY.md 8c fixture T0: same topology, small channels, used at odd spatial sizes.'''
 
+WEIGHT_TINY = dict(
+    input_channels_image=3, input_channels_depth=2,
+    n_filters_encoder_image=[8, 16, 32, 32, 32],
+    n_filters_encoder_depth=[8, 16, 32, 32, 32],
+    n_filters_decoder=[32, 16, 8, 8, 4])
+'''fusion_type 'weight' runs in the reference with five levels and equal branch widths only (src/networks.py:681, :742, :862).'''
+
+WEIGHT_WIDE = dict(
+    input_channels_image=3, input_channels_depth=2,
+    n_filters_encoder_image=[32, 64, 128, 256, 256],
+    n_filters_encoder_depth=[32, 64, 128, 256, 256],
+    n_filters_decoder=[256, 128, 64, 64, 32])
+'''the same envelope at the published image-branch widths.'''
+
 
 def make_radarnet_batch(seed, n=2, k=2, h=64, w=96, patch_w=32):
     '''

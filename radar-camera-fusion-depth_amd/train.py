@@ -9,8 +9,9 @@ from .fusionnet_model import FusionNetModel
 from .optim import FusedAdam
 
 
-def build_model(cfg=None, device='cuda', weight_initializer='kaiming_uniform', deconv_type='up'):
-    '''FusionNetModel with the shipped flags (bash/train_fusionnet_nuscenes.sh:27-40; deconv 'up' per src/fusionnet_main.py:190).'''
+def build_model(cfg=None, device='cuda', weight_initializer='kaiming_uniform', deconv_type='up', fusion_type='weight_and_project'):
+    '''FusionNetModel with the shipped flags (bash/train_fusionnet_nuscenes.sh:27-40; deconv 'up' per src/fusionnet_main.py:190).
+    fusion_type: the reference's --fusion_type (src/train_fusionnet.py:49); 'add' and 'concat' besides the shipped one.'''
     cfg = synth.PUBLISHED if cfg is None else cfg
     return FusionNetModel(
         input_channels_image=cfg['input_channels_image'],
@@ -18,7 +19,7 @@ def build_model(cfg=None, device='cuda', weight_initializer='kaiming_uniform', d
         encoder_type=['fusionnet18', 'batch_norm'],
         n_filters_encoder_image=cfg['n_filters_encoder_image'],
         n_filters_encoder_depth=cfg['n_filters_encoder_depth'],
-        fusion_type='weight_and_project',
+        fusion_type=fusion_type,
         decoder_type=['multiscale', 'batch_norm'],
         n_resolution_decoder=1,
         n_filters_decoder=cfg['n_filters_decoder'],
