@@ -633,6 +633,23 @@ int rcf_stem_weights_s2d(const float* w7_oihw, float* w4_oihw, int c_out, int c_
  * reference-side glue; also how an fp32 scatter result joins a bf16 gradient). */
 int rcf_convert(const void* src, int src_storage, void* dst, int dst_storage, long long n, int accumulate, void* stream);
 
+/* The per-sample metrics of validate() and of the evaluation block of run() (src/fusionnet_main.py:528-548, :826-843, with
+ * src/eval_utils.py:17-71): over the pixels of sample s with gt > 0 && gt > min_evaluate_depth && gt < max_evaluate_depth (fp32
+ * comparisons, like numpy's of a float32 array with a Python scalar), with o the output depth,
+ *   mae = mean |1000 gt - 1000 o|, rmse = sqrt(mean (1000 gt - 1000 o)^2)               (mm)
+ *   imae = mean |1/(0.001 gt) - 1/(0.001 o)|, irmse = sqrt(mean (...)^2)                 (1/km)
+ * and count = the number of such pixels (none: NaN in all four, as np.mean of an empty array).  Element arithmetic and every sum are
+ * fp64, in an order that depends on `pix` alone: a sample gives the same bits alone, inside a batch, on the 16-byte-load path (both
+ * sample bases 16-byte aligned) and on the scalar path.  No atomics.
+ * depth, ground_truth: n x pix fp32, contiguous (N x 1 x H x W).  workspace: RCF_EVAL_WORKSPACE_DOUBLES(n) doubles.
+ * results: capacity x 5 doubles (mae, rmse, imae, irmse, count per row).  cursor (device, int[2]): [0] = the next free row, [1] = rows
+ * dropped.  The call writes the rows cursor[0] .. cursor[0] + n - 1 and advances cursor[0] by n, so one recorded into a hipGraph fills
+ * the next n rows on every replay; when cursor[0] + n > capacity it writes no row at all, leaves cursor[0] and adds n to cursor[1]. */
+#define RCF_EVAL_BLOCKS 512 /* workspace slots (and at most that many workgroups) per sample */
+#define RCF_EVAL_WORKSPACE_DOUBLES(n) ((size_t)(n) * 5 * RCF_EVAL_BLOCKS)
+int rcf_eval_metrics(const float* depth, const float* ground_truth, int n, long long pix, float min_evaluate_depth,
+                     float max_evaluate_depth, double* workspace, double* results, int capacity, int* cursor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,7 +165,10 @@ _SIGNATURES['rcf_fuse_add_infer_b16'] = (c_int, [_P, _P, _P, _P, _P, c_longlong,
 _SIGNATURES['rcf_s2d_image_b16'] = (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P])
 _SIGNATURES['rcf_s2d_image_f32'] = (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P])
 _SIGNATURES['rcf_stem_weights_s2d'] = (c_int, [_P, _P, c_int, c_int, _P])
+_SIGNATURES['rcf_eval_metrics'] = (c_int, [_P, _P, c_int, c_longlong, c_float, c_float, _P, _P, c_int, _P, _P])
 '''Every symbol include/rcf_hip.h declares, with its ctypes signature.'''
+
+RCF_EVAL_BLOCKS = 512   # include/rcf_hip.h; RCF_EVAL_WORKSPACE_DOUBLES(n) = n * 5 * RCF_EVAL_BLOCKS
 
 _lib = None
 

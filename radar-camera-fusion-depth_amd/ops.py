@@ -683,6 +683,40 @@ def l1_loss_bwd(depth, gt, lidar, sums, upstream, w_lidar, ddepth, kind='l1'):
                                           depth.numel(), LOSS_KINDS[kind], _stream()), 'rcf_masked_loss_bwd')
 
 
+def eval_workspace_doubles(n):
+    """RCF_EVAL_WORKSPACE_DOUBLES(n) of include/rcf_hip.h."""
+    return int(n) * 5 * _lib.RCF_EVAL_BLOCKS
+
+
+def eval_metrics(output_depth, ground_truth, min_evaluate_depth, max_evaluate_depth, workspace, results, cursor):
+    """The validation metrics of every sample of an N x 1 x H x W (or N x H x W) fp32 pair (rcf_eval_metrics; src/fusionnet_main.py:
+    528-548): the rows cursor[0] .. cursor[0] + N - 1 of `results` (capacity x 5 fp64: mae, rmse, imae, irmse, count) are written and
+    cursor[0] (int32[2], device) advances by N, all on the current stream; nothing synchronises.  workspace: fp64, at least
+    eval_workspace_doubles(N) elements."""
+    for t in (output_depth, ground_truth, workspace, results, cursor):
+        if not t.is_cuda:
+            raise _lib.RcfError('rcf ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path' % t.device)
+    if output_depth.dtype != torch.float32 or ground_truth.dtype != torch.float32:
+        raise ValueError('eval_metrics: output_depth and ground_truth are float32; got %s / %s' % (output_depth.dtype, ground_truth.dtype))
+    if output_depth.shape != ground_truth.shape:
+        raise ValueError('eval_metrics: shapes differ: %s / %s' % (tuple(output_depth.shape), tuple(ground_truth.shape)))
+    if not (output_depth.dim() == 3 or (output_depth.dim() == 4 and output_depth.shape[1] == 1)) or output_depth.numel() == 0:
+        raise ValueError('eval_metrics: expected non-empty N x 1 x H x W or N x H x W; got %s' % (tuple(output_depth.shape),))
+    if not (output_depth.is_contiguous() and ground_truth.is_contiguous()):
+        raise ValueError('eval_metrics: output_depth and ground_truth must be contiguous')
+    n = output_depth.shape[0]
+    pix = output_depth.numel() // n
+    if workspace.dtype != torch.float64 or results.dtype != torch.float64 or cursor.dtype != torch.int32:
+        raise ValueError('eval_metrics: workspace and results are float64, cursor is int32')
+    if results.dim() != 2 or results.shape[1] != 5 or cursor.numel() != 2 or workspace.numel() < eval_workspace_doubles(n):
+        raise ValueError('eval_metrics: results is capacity x 5, cursor holds 2 elements, workspace eval_workspace_doubles(N)')
+    if not (workspace.is_contiguous() and results.is_contiguous() and cursor.is_contiguous()):
+        raise ValueError('eval_metrics: workspace, results and cursor must be contiguous')
+    check(_lib.load().rcf_eval_metrics(output_depth.data_ptr(), ground_truth.data_ptr(), n, pix, float(min_evaluate_depth),
+                                       float(max_evaluate_depth), workspace.data_ptr(), results.data_ptr(), results.shape[0],
+                                       cursor.data_ptr(), _stream()), 'rcf_eval_metrics')
+
+
 def outlier_removal(depth, kernel_size=7, threshold=1.5):
     """OutlierRemoval.remove_outliers (src/net_utils.py:591-638) on an N x 1 x H x W (or N x H x W) sparse depth map."""
     shape = depth.shape

@@ -108,6 +108,28 @@ def make_scatter_case(k, h, w, wc, seed, small_z):
     return crops, pts
 
 
+def make_eval_case(seed, n, h, w, density, sigma):
+    '''
+    Seeded inputs for the validation metrics (src/fusionnet_main.py:528-548): (output_depth, ground_truth), both N x 1 x H x W float32
+    numpy arrays.  ground_truth holds U[1, 80) m on a `density` fraction of the pixels and 0 elsewhere; output_depth is
+    ground_truth + N(0, sigma) clipped to the model's range (0.99, 100) where the ground truth is valid and U(0.99, 100) elsewhere.
+    sigma: metres, or a callable that maps the ground-truth array to a per-pixel sigma (an error that depends on the distance).
+    '''
+    rs = np.random.RandomState(seed)
+    shape = (n, 1, h, w)
+    gt = (rs.uniform(1.0, 80.0, size=shape) * (rs.rand(*shape) < density)).astype(np.float32)
+    sig = sigma(gt) if callable(sigma) else sigma
+    noisy = np.clip(gt + rs.standard_normal(shape) * sig, 0.99, 100.0)
+    out = np.where(gt > 0, noisy, rs.uniform(0.99, 100.0, size=shape)).astype(np.float32)
+    return out, gt
+
+
+def banded_sigma(near, mid, far):
+    '''A sigma for make_eval_case that depends on the distance: `near` below 10 m, `far` beyond 40 m, `mid` between.  The inverse
+    metrics are decided by the near pixels and the metric ones by the far pixels, so the two pairs can be moved against each other.'''
+    return lambda gt: np.where(gt > 40.0, far, np.where(gt < 10.0, near, mid))
+
+
 PUBLISHED = dict(
     input_channels_image=3, input_channels_depth=2,
     n_filters_encoder_image=[32, 64, 128, 256, 256, 256],
